@@ -10,7 +10,7 @@ identical results to the learner's `if done.any(): reset_done()`), SURVEY.md sec
 epochs.  `value` = env_num * 200 * K * n_gpus / wall.  Inputs (the action tapes) are resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N rank processes itself
@@ -105,7 +105,10 @@ class RolloutHandoff:
 
 
 def run_epochs(env, tapes, epochs, handoff):
-    """`epochs` bench steps: reset() + one fused 200-pass rollout each (+ the async hand-off)."""
+    """`epochs` bench steps: reset() + one fused 200-pass rollout each (+ the async hand-off).  Returns what a caller
+    receives from the last epoch: rollout()'s (obs, reward, cost, done) without a hand-off, else the gathered packed
+    rows (world, T, N, D + A + 3).  Only the last epoch's result is held, so the allocator sees what it always saw."""
+    last = None
     for ep in range(epochs):
         env.reset(check=False)           # the layout_size assert is checked once after the loop
         acts = tapes[ep % len(tapes)]
@@ -113,11 +116,47 @@ def run_epochs(env, tapes, epochs, handoff):
             handoff.submit(env.rollout(acts, packed=True)[4])
         elif handoff is not None:
             handoff.step(acts)           # TapeHandoff: dynamics pass here, observation pass on every rank
-        else:
+        elif ep + 1 < epochs:
             env.rollout(acts)
+        else:
+            last = env.rollout(acts)
     if handoff is not None:
         handoff.drain()
+        if isinstance(handoff, RolloutHandoff):
+            last = handoff.slots[(handoff.k - 1) % handoff.depth][2] if handoff.k else None
+        else:
+            last = handoff.rollout
     env.check_layouts()                  # engine.py:444 for every reset above (one sync)
+    return last
+
+
+DUMP_BYTES = 60_000_000          # --dump-outputs writes at most this much (the limit is 64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, last, obs_dim, act_dim):
+    """Write the arrays of the last timed epoch (run_epochs) as out_dir/<name>.npy, float32.  If they exceed DUMP_BYTES
+    together, every array keeps the same fixed, seeded sample of env columns (axis -2 of obs / action, -1 of the rest)."""
+    if isinstance(last, tuple):
+        arrs = dict(zip(("obs", "reward", "cost", "done"), last))
+    else:
+        D, A = obs_dim, act_dim
+        arrs = {"obs": last[..., :D], "action": last[..., D:D + A], "reward": last[..., D + A],
+                "cost": last[..., D + A + 1], "done": last[..., D + A + 2]}
+    N = arrs["reward"].shape[-1]
+    total = sum(a.numel() * 4 for a in arrs.values())
+    idx = None
+    if total > DUMP_BYTES:
+        k = N * DUMP_BYTES // total
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=k, replace=False))
+        idx_t = torch.from_numpy(idx).to(last[0].device if isinstance(last, tuple) else last.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        if idx is not None:
+            a = a.index_select(a.dim() - (2 if name in ("obs", "action") else 1), idx_t)
+        np.save(os.path.join(out_dir, name + ".npy"), a.to(torch.float32).cpu().numpy())
+    return {"dir": out_dir, "arrays": sorted(arrs), "env_columns": N if idx is None else int(len(idx)),
+            "env_sample_seed": None if idx is None else DUMP_SEED}
 
 
 PRECONDITION_MS = 60.0
@@ -823,6 +862,9 @@ def main():
                     help="repetitions of the [warm-up, timed] region; `value` is their median (default 5)")
     ap.add_argument("--no-precondition", action="store_true",
                     help="skip the `preconditioned` sibling measurement (one repetition behind 60 ms of torch.mm)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (obs, reward, cost, done) as "
+                         "DIR/<name>.npy, float32, at most 60 MB (a fixed seeded sample of env columns beyond that)")
     ap.add_argument("--child-extra", choices=sorted(CHILD_EXTRAS), help=argparse.SUPPRESS)
     ap.add_argument("--child-out", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -867,12 +909,15 @@ def main():
             return RolloutHandoff(world)
         return gxd.TapeHandoff(env, EP_LEN, sharded_sampler=sharded, expand=expand)
 
+    timed_out = {}                       # what the last timed epoch returned (--dump-outputs)
+
     def timed_region(handoff, warmup):
+        timed_out.clear()
         run_epochs(env, tapes, warmup, handoff)
         gxd.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_epochs(env, tapes, args.steps, handoff)
+        timed_out["last"] = run_epochs(env, tapes, args.steps, handoff)
         torch.cuda.synchronize()
         gxd.barrier()
         return gxd.max_over_ranks(time.perf_counter() - t0, device)
@@ -894,6 +939,10 @@ def main():
     # work in front of it.  The first repetition is the cold one (the firmware's clock ramp, ~13 ms on this pool, covers
     # it); it is reported with the others, and min / max give the spread.
     dt, dts, handoff = leg(True, "all", args.warmup, reps=args.reps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, timed_out["last"], env.obs_flat_size, env.action_space.shape[0])
+    timed_out.clear()
 
     env_steps = ENV_NUM * world * EP_LEN * args.steps
     value = env_steps / dt
@@ -986,6 +1035,8 @@ def main():
                                "note": "GX_FORCE_DIST=1: the N > 1 path (process group, barrier, max-over-ranks, tape hand-off "
                                        "with the collective issued, sharded sampler, all-tapes expansion) over a group of "
                                        "this many ranks -- a code-path run, not a scaling measurement"}
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if dt < 0.010:
         line["warning"] = f"timed region {dt*1e3:.2f} ms < 10 ms: use more --steps for a meaningful rate"
     if stepping_only is not None:

@@ -198,6 +198,8 @@ class TapeHandoff:
         x = torch.zeros(4, dtype=torch.float32, device=dev)
         y = torch.zeros(4 * self.world, dtype=torch.float32, device=dev)
         dist.all_gather_into_tensor(y, x)                  # the first collective builds the communicator and its stream
+        with torch.cuda.stream(self.stream):
+            torch.cuda._sleep(1)                           # the spinner's first launch loads its code object: untimed
         torch.cuda.synchronize(dev)
         cur = torch.cuda.current_stream(dev)
         for rnd in range(self.PROBE_ROUNDS):

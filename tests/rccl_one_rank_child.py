@@ -75,8 +75,15 @@ def main(report_path):
     h = gxd.TapeHandoff(a, T)
     del os.environ["GX_HANDOFF_QUEUE_PROBE"]
     assert h.collective and h.sharded and not h.host and h.world == 1
-    # the probe of the collective's hardware queue ran its rounds; the last stream it settled on runs beside the collective
-    assert len(h.queue_probe) == h.PROBE_ROUNDS and not h.queue_probe[-1][2], h.queue_probe
+    # the probe of the collective's hardware queue ran its rounds.  HIP spreads a process's streams over
+    # GPU_MAX_HW_QUEUES hardware queues (4 by default): with three or more, the last stream it settled on runs beside
+    # the collective; with two, the engine's streams and the collective's end up on one queue whatever is renewed, and
+    # every round must see the collective wait for the spinner
+    assert len(h.queue_probe) == h.PROBE_ROUNDS, h.queue_probe
+    if int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) >= 3:
+        assert not h.queue_probe[-1][2], h.queue_probe
+    else:
+        assert all(shared for _, _, shared in h.queue_probe), h.queue_probe
     report["queue_probe"] = h.queue_probe
     assert all(r.device.type == "cuda" for r in h.recv) and h.recv[0].data_ptr() != h.send[0].data_ptr()
     rng = np.random.default_rng(21)

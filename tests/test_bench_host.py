@@ -1,4 +1,4 @@
-"""Host-side logic of bench.py that needs no GPU: the round-over-round comparison block."""
+"""Host-side logic of bench.py that needs no GPU: the round-over-round comparison block and the --dump-outputs writer."""
 import json
 import os
 import sys
@@ -57,3 +57,36 @@ def test_comparable_values_ignore_what_is_not_a_rate():
                                      "closed_loop_policy_env_steps_per_s": {"error": "z"},
                                      "closed_loop_policy_wider_env_steps_per_s": {"hidden_128": 3.0, "hidden_256": "err"}})
     assert vals == {"value": 1.0, "other_robots.a": 2.0, "closed_loop_policy.hidden_128": 3.0}
+
+
+def test_dump_outputs_writes_the_last_epoch_within_the_byte_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    bench = _bench()
+    T, N, D, A = 3, 50, 4, 2
+    g = torch.Generator().manual_seed(1)
+    obs, rew, cost, done = (torch.rand(T, N, D, generator=g),) + tuple(torch.rand(T, N, generator=g) for _ in range(3))
+    # rollout()'s four tensors, small enough to go out whole
+    info = bench.dump_outputs(str(tmp_path / "whole"), (obs, rew, cost, done), D, A)
+    assert info["env_columns"] == N and info["env_sample_seed"] is None
+    for name, t in zip(("obs", "reward", "cost", "done"), (obs, rew, cost, done)):
+        a = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert a.dtype == np.float32
+        np.testing.assert_array_equal(a, t.numpy())
+    # the gathered packed rows (world, T, N, D + A + 3) of a hand-off, over the limit: the same env columns everywhere
+    act = torch.rand(T, N, A, generator=g)
+    packed = torch.cat([obs, act, rew[..., None], cost[..., None], done[..., None]], -1)[None]
+    monkeypatch.setattr(bench, "DUMP_BYTES", packed.numel() * 4 // 2)
+    runs = []
+    for k in range(2):
+        info = bench.dump_outputs(str(tmp_path / f"s{k}"), packed, D, A)
+        assert 0 < info["env_columns"] < N and info["arrays"] == ["action", "cost", "done", "obs", "reward"]
+        runs.append({n: np.load(tmp_path / f"s{k}" / f"{n}.npy") for n in info["arrays"]})
+        assert sum(a.nbytes for a in runs[-1].values()) <= bench.DUMP_BYTES
+    cols = [int(np.argmax((rew[0].numpy() == v))) for v in runs[0]["reward"][0, 0]]
+    assert cols == sorted(cols) and len(set(cols)) == len(cols)
+    np.testing.assert_array_equal(runs[0]["obs"][0], obs[:, cols].numpy())
+    np.testing.assert_array_equal(runs[0]["action"][0], act[:, cols].numpy())
+    np.testing.assert_array_equal(runs[0]["done"][0], done[:, cols].numpy())
+    for n in runs[0]:
+        np.testing.assert_array_equal(runs[0][n], runs[1][n])

@@ -1,16 +1,15 @@
 """the model constants carried by the HIP headers and by the CPU checker equal what
-tools/model_constants.py derives from the robot MJCF files (when those are available: they live in the
-reference checkout, which exists in the build container only), and the two carriers agree with each other
+tools/model_constants.py derives from the reference's robot MJCF files (stored as data under tests/golden/mjcf/),
+and the two carriers agree with each other
 and with the hand-restated tables of oracle/ant_np.py."""
 import os
 import re
 import sys
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-XML_DIR = "/root/reference/safe_rl_envs/safe_rl_envs/xmls"
+XML_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mjcf")       # the robot MJCF files, stored as data
 NUM = r'(-?[0-9]+\.?[0-9]*(?:[eE][-+]?[0-9]+)?)f'
 
 
@@ -75,7 +74,6 @@ def test_ant_constants_match_the_hand_restated_tables():
     assert _same_f32(HIP_ANT['kLC'], np.linalg.norm(m.ipos[ank]))
 
 
-@pytest.mark.skipif(not os.path.isdir(XML_DIR), reason="robot MJCF files (reference checkout) not present")
 def test_headers_match_the_mjcf_files():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import model_constants
@@ -92,7 +90,6 @@ def test_headers_match_the_mjcf_files():
     assert "0.005188790204786391" in txt and abs(0.005188790204786391 - derived['point']['kM']) < 1e-17
 
 
-@pytest.mark.skipif(not os.path.isdir(XML_DIR), reason="robot MJCF files (reference checkout) not present")
 def test_parser_agrees_with_hand_tables_on_the_ant():
     sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, ROOT)
     from mjcf_model import Model
@@ -106,7 +103,6 @@ def test_parser_agrees_with_hand_tables_on_the_ant():
     assert pm.timestep == ant_np.H
 
 
-@pytest.mark.skipif(not os.path.isdir(XML_DIR), reason="robot MJCF files (reference checkout) not present")
 def test_walker_tables_match_the_mjcf_file():
     """the generated tables carried by gx_robot_legs.h / gx_oracle_legs.inc are what the generator derives now,
     and the generator's parser agrees with the hand-restated tables of oracle/walker_np.py"""
@@ -172,7 +168,6 @@ def test_actuator_default_class_resolution(tmp_path):
     assert g2['biastype'] == 'none' and g2['gainprm'][0] == 2 and list(g2['biasprm']) == [0, -4, 0]
 
 
-@pytest.mark.skipif(not os.path.isdir(XML_DIR), reason="robot MJCF files (reference checkout) not present")
 def test_point_actuators_resolve_to_the_limited_velocity_servo():
     """point.xml:4-10,37-39: the <general gear=.3> actuators inherit ctrlrange +-1, forcerange +-.05 and
     the affine bias (0, 0, -1) of <velocity>; Engine.action_space follows actuator_ctrllimited

@@ -1,25 +1,21 @@
 """SURVEY.md row f4, the `World.build` half -- and the ONE artefact of this path the reference checkout holds.
 
-`/root/reference/safe_rl_libX/result.xml` is the MJCF `World.build` itself wrote (world.py:331-332) for
+The reference's `safe_rl_libX/result.xml` is the MJCF `World.build` itself wrote (world.py:331-332) for
 Goal_Point_8Hazards.  tools/world_model.py restates `Engine.build_world_config` (engine.py:335-384) and `World.build`
 (world.py:104-326) without xmltodict / mujoco; here the assembled tree must equal that file element by element -- tags,
 order, attribute names, attribute STRINGS -- and the index tables derived from it (engine.py:302-316) must be what the
-kernels and the CPU checker hard-code.  The file is read in place (it does not travel and is never copied): the tests
-that need it skip where /root/reference is absent."""
+kernels and the CPU checker hard-code.  That file and the robot MJCF files are stored as data under tests/golden/mjcf/."""
 import os
 import sys
 import xml.etree.ElementTree as ET
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, ROOT)
-XML_DIR = "/root/reference/safe_rl_envs/safe_rl_envs/xmls"
-RESULT_XML = "/root/reference/safe_rl_libX/result.xml"
-needs_ref = pytest.mark.skipif(not (os.path.isdir(XML_DIR) and os.path.isfile(RESULT_XML)),
-                               reason="reference checkout (robot MJCF files, result.xml) not present")
+XML_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mjcf")       # the robot MJCF files, stored as data
+RESULT_XML = os.path.join(XML_DIR, "result_goal_point_8hazards.xml")
 
 import world_model as wm  # noqa: E402
 from guardx_amd import configuration  # noqa: E402
@@ -29,7 +25,6 @@ def _ref():
     return wm.Node.from_element(ET.parse(RESULT_XML).getroot())
 
 
-@needs_ref
 def test_assembled_world_equals_the_reference_result_xml():
     root, _ = wm.assemble(dict(configuration("Goal_Point_8Hazards")), XML_DIR)
     ref = _ref()
@@ -41,7 +36,6 @@ def test_assembled_world_equals_the_reference_result_xml():
     assert root.signature() == ref.signature()
 
 
-@needs_ref
 def test_the_facts_the_hot_path_rests_on_are_in_the_reference_file():
     """read off the reference's own result.xml (not off the restatement): what DESIGN.md sections 0.1 / 2 assume"""
     ref = _ref()
@@ -78,7 +72,6 @@ def test_the_facts_the_hot_path_rests_on_are_in_the_reference_file():
     assert np.float32(rb.attrib['pos'].split()[2]) - np.float32(sphere.attrib['size']) == np.float32(0.0)
 
 
-@needs_ref
 def test_index_tables_equal_what_kernels_and_checker_hard_code(oracle):
     """engine.py:302-316 on the assembled model of every robot: the robot body is body 1 and its joints come first
     (qpos[:nq] / qvel[:nv] of the world arrays are the robot's: engine.py:760-766), robot_x / robot_y sit where
