@@ -1,4 +1,4 @@
-"""Build libguardx_hip.so (gfx950) in-tree with hipcc.
+"""Build libguardx_hip.so and libguardx_critic.so (gfx950) in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -62,6 +62,13 @@ def _extra(src):
 BUILD_ID_FILE = os.path.join(LIB_DIR, "BUILD_ID")
 LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 
+# The batched cost critic (include/guardx_critic.h) is a library of its own with its own build identity, so that it
+# leaves the sources, the flags and the build id of libguardx_hip.so -- and the profiles taken on that build -- alone.
+CRITIC_LIB = os.path.join(LIB_DIR, "libguardx_critic.so")
+CRITIC_SOURCES = ["gx_critic.hip"]
+CRITIC_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_critic.h")]
+CRITIC_BUILD_ID_FILE = os.path.join(LIB_DIR, "CRITIC_BUILD_ID")
+
 
 _COMPILER = None
 
@@ -101,6 +108,20 @@ def source_hash():
     return h.hexdigest()[:24]
 
 
+def critic_source_hash():
+    """source_hash() of libguardx_critic.so: its sources, every project header they include, FLAGS and the compiler
+    (compiled in as gxc_build_id() and checked at load time, guardx_amd/_critic_native.py)."""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(compiler_id().encode() + b"\0")
+    for n in sorted(set(CRITIC_SOURCES) | set(CRITIC_HEADERS)):
+        h.update(n.encode() + b"\0")
+        with open(os.path.join(CSRC, n), "rb") as f:
+            h.update(f.read())
+    h.update(repr(FLAGS).encode())
+    return h.hexdigest()[:24]
+
+
 def _obj(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
 
@@ -117,6 +138,18 @@ def needs_build():
     return not os.path.exists(LIB) or built_id() != source_hash()
 
 
+def built_critic_id():
+    try:
+        with open(CRITIC_BUILD_ID_FILE) as f:
+            return f.read().strip()
+    except OSError:
+        return None
+
+
+def critic_needs_build():
+    return not os.path.exists(CRITIC_LIB) or built_critic_id() != critic_source_hash()
+
+
 def _dep_hash(src):
     """identity of one object file: its source, every header, its flags (objects are reused across builds)"""
     import hashlib
@@ -130,15 +163,18 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file)."""
+    and rename into place (nobody can dlopen a half-written file).  Both libraries; returns the path of
+    libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            if not force and not needs_build():
-                return LIB
-            return _build_locked(force, verbose, jobs)
+            if force or needs_build():
+                _build_locked(force, verbose, jobs)
+            if force or critic_needs_build():
+                _build_critic_locked(verbose)
+            return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
@@ -181,6 +217,23 @@ def _build_locked(force, verbose, jobs):
     return LIB
 
 
+def _build_critic_locked(verbose):
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    bid = critic_source_hash()
+    tmp = CRITIC_LIB + ".tmp.%d" % os.getpid()
+    cmd = [hipcc] + FLAGS + ['-DGXC_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
+          [os.path.join(CSRC, s) for s in CRITIC_SOURCES]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, CRITIC_LIB)
+    with open(CRITIC_BUILD_ID_FILE + ".tmp", "w") as f:
+        f.write(bid + "\n")
+    os.replace(CRITIC_BUILD_ID_FILE + ".tmp", CRITIC_BUILD_ID_FILE)
+    return CRITIC_LIB
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
+    print("critic build id", built_critic_id())

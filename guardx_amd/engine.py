@@ -795,13 +795,38 @@ class Engine:
     def _policy_floats(D, A, h):
         return 2 * (h * D + h + h * h + h) + (A + 1) * h + (A + 1) + A
 
-    def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0)):
+    @staticmethod
+    def pack_critic(critic, device=None):
+        """Flatten a cost critic (`ac.vc` of the CPO-family cores, safe_rl_libX/cpo/cpo_core.py: anything with .v_net,
+        or the nn.Sequential Linear/Tanh/Linear/Tanh/Linear[/Identity] itself) into the layout of
+        guardx_amd.critic.critic_values and rollout_policy(..., cost_critic=): W1 b1 W2 b2 W3 b3, float32."""
+        net = getattr(critic, 'v_net', critic)
+        mods = [m for m in net if not isinstance(m, torch.nn.Identity)]
+        lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
+        if len(lin) != 3:
+            raise NotImplementedError("the cost critic pass supports two hidden layers (--l 2)")
+        if [type(m) for m in mods] != [torch.nn.Linear, torch.nn.Tanh] * 2 + [torch.nn.Linear]:
+            raise NotImplementedError("the cost critic pass supports Tanh hidden activations and a linear output only")
+        if lin[0].out_features != lin[1].out_features or lin[1].in_features != lin[0].out_features \
+                or lin[2].in_features != lin[1].out_features:
+            raise NotImplementedError("the cost critic pass supports two hidden layers of equal width")
+        if lin[0].out_features not in Engine.POLICY_HIDDEN:
+            raise NotImplementedError(f"the cost critic pass supports hidden widths {Engine.POLICY_HIDDEN}")
+        if lin[2].out_features != 1:
+            raise NotImplementedError("the cost critic pass supports one output")
+        flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for m in lin for t in (m.weight, m.bias)])
+        return flat.to(device) if device is not None else flat
+
+    def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of
         trpo_core.py:110-173 evaluated there).  `params` = pack_actor_critic(ac); the hidden width is read off its
         size.  h = 64: ONE kernel launch for the whole rollout; h = 128 / 192 / 256 (the weights do not fit the fused
         kernel's LDS): two launches per control step, same results.
         Returns a dict of time-major tensors: obs (T,N,D) [what the policy saw], act, mu (T,N,A),
-        logp, val, rew, cost, done (T,N), plus obs_last (N,D), val_last (N,), logstd (A,)."""
+        logp, val, rew, cost, done (T,N), plus obs_last (N,D), val_last (N,), logstd (A,).
+        cost_critic = pack_critic(ac.vc) (CPO-family learners, cpo.py:600): the dict also holds vc (T,N) = Vc(obs[t])
+        and vc_last (N,) = Vc(obs_last), from one batched pass over the recorded observations right after the rollout,
+        on the same stream (guardx_amd.critic), with the bits of the value head; its width may differ from the actor's."""
         if obs0 is None:
             obs0 = self._obs
         if obs0 is None:
@@ -814,10 +839,21 @@ class Engine:
         if hidden is None:
             raise ValueError(f"params has {params.numel()} floats; expected one of "
                              f"{[self._policy_floats(D, A, h) for h in self.POLICY_HIDDEN]} (hidden {self.POLICY_HIDDEN})")
+        if cost_critic is not None:
+            from . import critic as _critic
+            cost_critic = cost_critic.to(device=self.device, dtype=torch.float32).contiguous()
+            if _critic.critic_hidden(D, cost_critic.numel()) is None:
+                raise ValueError(f"cost_critic has {cost_critic.numel()} floats; expected one of "
+                                 f"{[_critic.critic_floats(D, h) for h in _critic.HIDDEN]} (hidden {_critic.HIDDEN})")
+            _critic._critic_native.load()     # a missing critic library fails here, before anything is launched
         self._rd_obs = None
         out = dict(obs=self._new(T, N, D), act=self._new(T, N, A), logp=self._new(T, N), val=self._new(T, N),
                    mu=self._new(T, N, A), rew=self._new(T, N), cost=self._new(T, N), done=self._new(T, N),
                    obs_last=self._new(N, D), val_last=self._new(N), logstd=self._new(A))
+        if cost_critic is not None:
+            # obs and obs_last as the two views of one (T + 1, N, D) block: one pass over T N + N rows
+            rows = self._new(T + 1, N, D)
+            out['obs'], out['obs_last'] = rows[:T], rows[T]
         pol = _native.GxPolicy()
         pol.struct_size = C.sizeof(_native.GxPolicy)
         pol.hidden = hidden
@@ -828,6 +864,9 @@ class Engine:
             out['logp'].data_ptr(), out['val'].data_ptr(), out['mu'].data_ptr(), out['rew'].data_ptr(),
             out['cost'].data_ptr(), out['done'].data_ptr(), out['obs_last'].data_ptr(),
             out['val_last'].data_ptr(), out['logstd'].data_ptr(), self._stream()))
+        if cost_critic is not None:
+            vc = _critic.critic_values(cost_critic, rows)
+            out['vc'], out['vc_last'] = vc[:T], vc[T]
         self._obs, self._reward, self._done = out['obs_last'], out['rew'][-1], out['done'][-1]
         self._info = {'cost': out['cost'][-1]}
         return out

@@ -143,3 +143,28 @@ def gae_rollout(rew, val, done, last_val=None, gamma=0.99, lam=0.95):
                                      float(gamma), float(lam), adv.data_ptr(), ret.data_ptr(),
                                      C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))))
     return adv, ret
+
+
+def cost_rollout_batch(out, gamma=0.99, lam=0.95):
+    """A rollout_policy(..., cost_critic=pack_critic(ac.vc)) result as the batch DeviceCostRolloutBuffer.get() returns
+    after CPO's collection loop (cpo.py:596-660): store() every step, finish_path() with v = vc = 0 for the envs done at
+    that step, a closing finish_path() over every env without bootstrap.  Env-major, flattened:
+    obs act ret adv cost_ret adc logp mu logstd; adv normalised per env, adc centred per env only (cpo.py:142-175)."""
+    for k in ('vc', 'rew', 'val', 'cost', 'done', 'obs'):
+        if k not in out:
+            raise KeyError(f"cost_rollout_batch needs out['{k}'] (rollout_policy(..., cost_critic=...))")
+    T, N = out['rew'].shape
+    adv, ret = gae_rollout(out['rew'], out['val'], out['done'], None, gamma, lam)
+    adc, cost_ret = gae_rollout(out['cost'], out['vc'], out['done'], None, gamma, lam)
+    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
+    adv, adc = env_major(adv), env_major(adc)
+    lib = _native.load()
+    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))
+    _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1, stream))
+    _native.check(lib.gx_adv_normalize(N, T, adc.data_ptr(), 0, stream))
+    A = out['act'].shape[-1]
+    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
+                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
+                cost_ret=env_major(cost_ret).view(N * T), adc=adc.view(N * T),
+                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
+                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous())
