@@ -10,7 +10,13 @@ identical results to the learner's `if done.any(): reset_done()`), SURVEY.md sec
 epochs.  `value` = env_num * 200 * K * n_gpus / wall.  Inputs (the action tapes) are resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+A plain run does only what `value` needs: set up, the --reps repetitions of [W warm-up, K timed epochs],
+--dump-outputs, the line.  --full adds every other measurement and comparison after the headline: the
+`preconditioned` sibling, `roofline`, at N > 1 `stepping_only` and `legs`, the supplementary extras (other
+robots, policy rollouts, the bandwidth regime, ...), `vs_previous_round` and `cpu_baseline`.  The headline
+region is the same in both.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N rank processes itself
@@ -856,12 +862,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)     # bench steps = 200-pass epochs
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement and comparison (preconditioned, roofline, "
+                         "the N > 1 legs, the supplementary extras, vs_previous_round, cpu_baseline); off: the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the supplementary extras")
     ap.add_argument("--reps", type=int, default=5,
                     help="repetitions of the [warm-up, timed] region; `value` is their median (default 5)")
     ap.add_argument("--no-precondition", action="store_true",
-                    help="skip the `preconditioned` sibling measurement (one repetition behind 60 ms of torch.mm)")
+                    help="with --full: skip the `preconditioned` sibling measurement (one repetition behind 60 ms of torch.mm)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (obs, reward, cost, done) as "
                          "DIR/<name>.npy, float32, at most 60 MB (a fixed seeded sample of env columns beyond that)")
@@ -948,7 +957,7 @@ def main():
     value = env_steps / dt
     stepping_only = None
     legs = None
-    if gather:
+    if gather and args.full:
         w2 = max(4, args.warmup)         # a change of the layout source costs up to three inline samplers
         W = env.obs_flat_size + 2 + 3
 
@@ -999,22 +1008,23 @@ def main():
                                       "every rank samples all candidates (shared key)"),
                    "point_actuators": "mjcf defaults inherited (DESIGN.md 0.1)"},
     }
-    try:   # the 8-GPU hand-off as arithmetic (it cannot be measured on a one-GPU box): bytes on the wire vs the epoch
-        shard_bytes = int(handoff.n if hasattr(handoff, "n") else sum(env.tape_floats(EP_LEN))) * 4
-        line["handoff_model"] = {
-            "shard_bytes_per_rank_per_epoch": shard_bytes,
-            "packed_rows_bytes_per_rank_per_epoch": int(EP_LEN * ENV_NUM * (env.obs_flat_size + 2 + 3) * 4),
-            "received_per_rank_at_8_gpus_bytes": 7 * shard_bytes,
-            "allgather_ms_at_8_gpus_310GBps": round(7 * shard_bytes / 310e9 * 1e3, 4),
-            "note_n1": "at N = 1 no hand-off runs; the shard here is the bare tape -- at N > 1 each rank's block of valid "
-                       "layouts (~0.5 MB) rides in its tail",
-            "ms_per_step_this_run": round(dt / args.steps * 1e3, 4),
-            "note": "one async all-gather of the dynamics tape per epoch (36 B per env-step: qpos, qvel, action, one word for "
-                    "done and the layout rows; at N > 1 plus the rank's export block of valid layouts, ~0.5 MB), overlapped "
-                    "with the following epoch; 310 GB/s = a realistic all-gather bus "
-                    "bandwidth over 7 xGMI links (537 GB/s peak per direction); arithmetic, not a measurement"}
-    except Exception as exc:  # noqa: BLE001
-        line["handoff_model"] = {"error": f"{type(exc).__name__}: {exc}"[:200]}
+    if args.full:
+        try:   # the 8-GPU hand-off as arithmetic (it cannot be measured on a one-GPU box): bytes on the wire vs the epoch
+            shard_bytes = int(handoff.n if hasattr(handoff, "n") else sum(env.tape_floats(EP_LEN))) * 4
+            line["handoff_model"] = {
+                "shard_bytes_per_rank_per_epoch": shard_bytes,
+                "packed_rows_bytes_per_rank_per_epoch": int(EP_LEN * ENV_NUM * (env.obs_flat_size + 2 + 3) * 4),
+                "received_per_rank_at_8_gpus_bytes": 7 * shard_bytes,
+                "allgather_ms_at_8_gpus_310GBps": round(7 * shard_bytes / 310e9 * 1e3, 4),
+                "note_n1": "at N = 1 no hand-off runs; the shard here is the bare tape -- at N > 1 each rank's block of valid "
+                           "layouts (~0.5 MB) rides in its tail",
+                "ms_per_step_this_run": round(dt / args.steps * 1e3, 4),
+                "note": "one async all-gather of the dynamics tape per epoch (36 B per env-step: qpos, qvel, action, one word "
+                        "for done and the layout rows; at N > 1 plus the rank's export block of valid layouts, ~0.5 MB), "
+                        "overlapped with the following epoch; 310 GB/s = a realistic all-gather bus "
+                        "bandwidth over 7 xGMI links (537 GB/s peak per direction); arithmetic, not a measurement"}
+        except Exception as exc:  # noqa: BLE001
+            line["handoff_model"] = {"error": f"{type(exc).__name__}: {exc}"[:200]}
     line["repetitions"] = {
         "n": len(dts), "values": [round(env_steps / t, 1) for t in dts],
         "min": round(env_steps / max(dts), 1), "max": round(env_steps / min(dts), 1),
@@ -1022,7 +1032,7 @@ def main():
         "note": "`value` = the median of these: each repetition is W untimed warm-up epochs + K timed epochs between "
                 "barrier + synchronize (max over ranks), run back to back; the first starts from the idle GPU the "
                 "process start leaves (inside the firmware's clock ramp), no filler work precedes any of them"}
-    if not args.no_precondition:
+    if args.full and not args.no_precondition:
         # the round-2..4 headline, kept as a sibling: ONE repetition behind 60 ms of unrelated GPU work (torch.mm)
         precond = precondition_clocks(device)
         dtp, _, _ = leg(True, "all", args.warmup)
@@ -1044,11 +1054,12 @@ def main():
     if legs is not None:
         line["legs"] = legs
     if rank == 0:
-        try:
-            line["roofline"] = roofline_rollout(ENV_NUM, EP_LEN, 30, device)
-        except Exception as exc:  # noqa: BLE001
-            line["roofline"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
-        if not args.no_extras and world == 1:
+        if args.full:
+            try:
+                line["roofline"] = roofline_rollout(ENV_NUM, EP_LEN, 30, device)
+            except Exception as exc:  # noqa: BLE001
+                line["roofline"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
+        if args.full and not args.no_extras and world == 1:
             # supplementary measurements; none of them may take the headline line down with it
             def extra(key, fn):
                 try:
@@ -1084,12 +1095,12 @@ def main():
             # in a fresh process, as each of these tasks would run on its own (same reason as multi_gpu_rehearsal: after the
             # dozen engines and streams of the extras above, HIP's stream -> hardware-queue assignment costs ~3 %)
             extra("other_robots", lambda: in_fresh_process("other_robots", device))
-        if world == 1:
+        if args.full and world == 1:
             try:
                 line["vs_previous_round"] = vs_previous_round(line)
             except Exception as exc:  # noqa: BLE001
                 line["vs_previous_round"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as exc:  # noqa: BLE001

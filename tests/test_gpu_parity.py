@@ -1075,7 +1075,8 @@ def test_bench_two_ranks_on_one_gpu_rehearsal(torch_cuda):
     tape hand-off ring with the layout sampler sharded over the two ranks (each samples half of the candidates of the
     reset after next, the rows ride on the tape all-gather, also over gloo), every leg the line reports at N > 1
     (`value` as the median of --reps repetitions, stepping_only, unsharded_sampler, local_expand, preconditioned), the deferred layout check of every leg, ONE
-    JSON line from rank 0 -- not the rate (gloo through host memory is two orders of magnitude slower than xGMI)."""
+    JSON line from rank 0 -- not the rate (gloo through host memory is two orders of magnitude slower than xGMI).
+    The legs beside `value` are what --full adds."""
     import json
     import os
     import subprocess
@@ -1085,7 +1086,8 @@ def test_bench_two_ranks_on_one_gpu_rehearsal(torch_cuda):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--reps", "3", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--reps", "3", "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                         timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -1100,6 +1102,35 @@ def test_bench_two_ranks_on_one_gpu_rehearsal(torch_cuda):
     assert reps["n"] == 3 and reps["min"] <= line["value"] <= reps["max"] and line["value"] in reps["values"]
     assert line["config"]["layout_sampler"].startswith("sharded")
     assert line["legs"]["unsharded_sampler"]["value"] > 0 and line["legs"]["local_expand"]["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(torch_cuda, tmp_path):
+    """`bench.py --gpus 1` without --full: the headline repetitions, the dumped arrays and the line -- none of the
+    measurements and comparisons that --full adds after them"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GX_FORCE_DIST"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--reps", "3", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "env-steps/sec" and line["unit"] == "env-steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["repetitions"]["n"] == 3 and line["value"] in line["repetitions"]["values"]
+    assert line["dumped_outputs"]["arrays"] == ["cost", "done", "obs", "reward"]
+    assert sorted(os.listdir(tmp_path)) == ["cost.npy", "done.npy", "obs.npy", "reward.npy"]
+    for key in ("preconditioned", "roofline", "handoff_model", "stepping_only", "legs", "other_robots", "reset_done_heavy",
+                "roofline_large_batch", "api_step_loop_env_steps_per_s", "vs_previous_round", "cpu_baseline"):
+        assert key not in line, key
 
 
 def test_tape_handoff_is_refused_where_it_does_not_apply(torch_cuda):

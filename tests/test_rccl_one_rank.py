@@ -61,10 +61,10 @@ def test_dist_path_over_a_one_rank_rccl_group(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_one_gpu_over_a_forced_one_rank_rccl_group():
-    """`GX_FORCE_DIST=1 python bench.py --gpus 1`: the N > 1 bench path (process group, barrier + max-over-ranks timing,
+    """`GX_FORCE_DIST=1 python bench.py --gpus 1 --full`: the N > 1 bench path (process group, barrier + max-over-ranks timing,
     tape hand-off with the sharded sampler, all four legs) over RCCL with one rank; one JSON line"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--no-extras", "--no-cpu-baseline"], env=_dist_env(NCCL_DEBUG="WARN"), capture_output=True,
+                          "--full", "--no-extras", "--no-cpu-baseline"], env=_dist_env(NCCL_DEBUG="WARN"), capture_output=True,
                          text=True, timeout=800)
     assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -44,7 +44,7 @@ for rb in swimmer ant walker; do   # the two-kernel rollout of the other robots 
 done
 kt sampler $RST
 pmc sampler SQ SQ_INSTS_VALU SQ_WAVES SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_BUSY_CYCLES -- $RST
-kt bench_noextras python3 bench.py --no-cpu-baseline --no-extras
+kt bench_noextras python3 bench.py --full --no-cpu-baseline --no-extras
 # round 4: one GPU playing rank 0 of 8 in the default multi-GPU epoch (per-kernel times of a rank's epoch), the step-wise
 # policy kernels of the wider networks, the 18-object sampler of the synthetic config 5
 kt rehearsal_rank0_of_8 python3 tools/rehearse_rank.py --world 8 --epochs 30

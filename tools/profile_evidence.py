@@ -180,7 +180,7 @@ def readme_rows():
                          f"(n/a = the form without that phase), {' / '.join(valu)} M VALU wave-instructions"))
     if _have("bench_noextras_kernel_stats.csv"):
         f = "bench_noextras_kernel_stats.csv"
-        rows.append((f"`{TAG}_{f}`", "`... -- python3 bench.py --no-cpu-baseline --no-extras`",
+        rows.append((f"`{TAG}_{f}`", "`... -- python3 bench.py --full --no-cpu-baseline --no-extras`",
                      f"the headline run under the profiler, per epoch: `sample_phase0/1/2` {_kt(f, 'sample_phase0')} / "
                      f"{_kt(f, 'sample_phase1')} / {_kt(f, 'sample_phase2')} us on the side stream; `reset_apply` {_kt(f, 'reset_apply')}, "
                      f"`dyn_tape` {_kt(f, 'dyn_tape_kernel')}, `obs_tape` {_kt(f, 'obs_tape_kernel')} us on the caller's stream beside them"))
@@ -190,7 +190,7 @@ def readme_rows():
                      f"closed-loop policy rollout by width: the fused kernels (one launch per 200 steps) `group_rollout_kernel<.., 2>` "
                      f"(64, weights in LDS) {_kt(f, ', true, 2>(')} us, `<.., 3>` (128, weights in registers) {_kt(f, ', true, 3>(')} us, "
                      f"`<.., 192>` / `<.., 256>` (weights streamed from L2) {_kt(f, ', true, 192>(')} / {_kt(f, ', true, 256>(')} us"))
-    for name, cmd in (("bench_driver_style.json", "`python bench.py --steps 20 --warmup 5`"), ("bench_full.json", "`python bench.py`")):
+    for name, cmd in (("bench_driver_style.json", "`python bench.py --steps 20 --warmup 5 --full`"), ("bench_full.json", "`python bench.py --full`")):
         if _have(name):
             l = _json_line(name)
             oth = l.get("other_robots", {})
@@ -236,7 +236,7 @@ def readme_rows():
                      f"packed rollout and to the CPU checker"))
     if _have("bench_force_dist_one_rank.json"):
         l = _json_line("bench_force_dist_one_rank.json")
-        rows.append((f"`{TAG}_bench_force_dist_one_rank.json`", "`GX_FORCE_DIST=1 python bench.py --gpus 1 --steps 4 --warmup 2 --no-extras`",
+        rows.append((f"`{TAG}_bench_force_dist_one_rank.json`", "`GX_FORCE_DIST=1 python bench.py --gpus 1 --steps 4 --warmup 2 --full --no-extras`",
                      f"the N > 1 bench path over a one-rank `{l.get('forced_dist', {}).get('backend')}` group (a code-path run, not a "
                      f"rate): all legs present -- `value` {_M(l['value'])}, stepping_only {_M(l['stepping_only']['value'])}, "
                      f"unsharded_sampler {_M(l['legs']['unsharded_sampler']['value'])}, local_expand {_M(l['legs']['local_expand']['value'])}"))
