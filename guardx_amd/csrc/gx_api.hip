@@ -494,8 +494,19 @@ extern "C" gx_status gx_create(const gx_config* cfg, gx_engine** out)
         if (err == hipSuccess) err = hipMemcpy(e->haz_bounds, hb.data(), sizeof(float4) * hb.size(), hipMemcpyHostToDevice);
         sp.haz_bounds = e->haz_bounds;
     }
+    // The sampler's key tape (gx_kernels.hip, sample_phase1_kernel): per pool, like the survivor records, so two samplers
+    // in flight at once (inline and prefetch, the ring of three) never share one.  Capacity in phase-1 survivors: 0.5 M
+    // (320 MB with 8 hazards) holds the ~250 k of the reference's arena; survivors beyond it walk their chain again in
+    // phase 2.  GX_SAMPLE_TAPE_CAP (tests): another capacity, down to 0 -- the pool is the same whatever it is.
+    const int tape_objs = sample_tape_objects(sp);
+    int tape_cap = (int)(M < 524288 ? M : 524288);
+    if (const char* ev = getenv("GX_SAMPLE_TAPE_CAP")) tape_cap = atoi(ev) >= 0 ? atoi(ev) : tape_cap;
     for (int i = 0; i < gx_engine::kPools; ++i) {
         Pool& pl = e->pools[i];
+        if (tape_objs > 0 && err == hipSuccess) { // written before it is read: no fill (at least one slot: cap 0 is valid)
+            err = hipMalloc((void**)&pl.key_tape, sizeof(uint2) * 10 * tape_objs * (size_t)(tape_cap > 0 ? tape_cap : 1));
+            pl.tape_cap = tape_cap;
+        }
         const size_t tile = (size_t)sample_compact_tile();
         alloc((void**)&pl.cand_ok, (M + tile - 1) / tile * tile);
         alloc((void**)&pl.cand_xy, sizeof(float2) * M * e->nobj_total);
@@ -569,7 +580,7 @@ extern "C" gx_status gx_destroy(gx_engine* e)
         if (q) (void)hipFree(q);
     for (int i = 0; i < gx_engine::kPools; ++i) {
         Pool& pl = e->pools[i];
-        void* pb[] = {pl.cand_ok, pl.cand_xy, pl.blk_cnt, pl.cand_of, pl.layout_size, pl.n_surv, pl.surv, pl.surv0, pl.fake};
+        void* pb[] = {pl.cand_ok, pl.cand_xy, pl.blk_cnt, pl.cand_of, pl.layout_size, pl.n_surv, pl.surv, pl.surv0, pl.fake, pl.key_tape};
         for (void* q : pb)
             if (q) (void)hipFree(q);
         if (e->pool_ready[i]) (void)hipEventDestroy(e->pool_ready[i]);
@@ -766,7 +777,9 @@ extern "C" gx_status gx_sample_shard(gx_engine* e, int32_t shard, int32_t n_shar
     const int tile = sample_compact_tile();
     const int padded = (sp.M + tile - 1) / tile * tile;
     if (padded > sp.M) GX_HIP(hipMemsetAsync(e->pools[tgt].cand_ok + sp.M, 0, (size_t)(padded - sp.M), s));
-    GX_HIP(launch_sample(sp, e->pools[tgt], s));
+    Pool shard_pool = e->pools[tgt];
+    shard_pool.key_tape = nullptr; // a shard samples without the key tape
+    GX_HIP(launch_sample(sp, shard_pool, s));
     launch_pool_export(e->pools[tgt], e->nobj_total, reinterpret_cast<float2*>(d_rows), cap, d_count, s);
     GX_HIP(hipGetLastError());
     return GX_OK;

@@ -37,7 +37,9 @@ struct Pool {
     int* n_surv;       // [2] phase-1 survivors, phase-0 survivors
     uint32_t* surv;    // [M][32] phase-1 survivor records
     uint32_t* surv0;   // [M][8] phase-0 survivor records
-    float* fake;       // null, or [M][NQ+NV+4]: reset_done's fake step (engine.py:719-724) from rest at the robot
+    uint2* key_tape;   // null, or [sample_tape_objects() * 10][tape_cap]: the hazard try keys of phase 1's survivors, by
+    int tape_cap;      // phase-1 slot (survivors at slot >= tape_cap have none: phase 2 walks their chain again)
+    float* fake;     // null, or [M][NQ+NV+4]: reset_done's fake step (engine.py:719-724) from rest at the robot
                        // position of valid layout c (row c of the compacted list): qpos, qvel, pose -- robots that move at rest
 };
 
@@ -55,6 +57,9 @@ void launch_step(const Params& p, const DevBuffers& b, const float* act, float* 
 int sample_compact_tile(); // candidates per block of the ordered compaction: cand_ok is padded to a multiple of it
 // returns the status of the event record it enqueues (ordering-critical: never dropped)
 hipError_t launch_sample(const SampleParams& sp, const Pool& pl, hipStream_t s, hipEvent_t after_phase1 = nullptr);
+// objects (hazards + pillars) whose sampler has a key tape (Pool::key_tape), 0 for none; Pool::key_tape is used only
+// when nobj_total - 2 equals it and the sampler is not the fused form
+int sample_tape_objects(const SampleParams& sp);
 // sharded layout sampling: a shard's valid layouts out (candidate order), the gathered shards in as the pool
 // `hdr`: null, or the 4-word header of a piggy-backed export block whose words 1..3 become (k0, k1, tag)
 void launch_pool_export(const Pool& pl, int nobj_total, float2* rows, int cap, int* count, hipStream_t s,

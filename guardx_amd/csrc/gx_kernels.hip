@@ -6,6 +6,7 @@
 #include "gx_robot.h"
 #include "gx_policy.h"
 #include <cstdlib>
+#include <utility>
 
 namespace gx {
 
@@ -105,13 +106,30 @@ __global__ __launch_bounds__(kSampleBlock) void sample_phase0_kernel(SampleParam
     }
 }
 
-// phase 1 (goal-feasible candidates, 220 blocks): hazard links, the 10 robot tries
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void sample_phase1_kernel(SampleParams sp,
-                                                                     const int* __restrict__ n_surv0,
-                                                                     const uint32_t* __restrict__ surv0,
-                                                                     int* __restrict__ n_surv,
-                                                                     uint32_t* __restrict__ surv)
+// phase 1 (goal-feasible candidates, 220 blocks): hazard links, the 10 robot tries.
+//
+// kTape > 0: the sampler has kTape objects (hazards + pillars) and a key tape.  The walk is unrolled, so the 10 * kTape
+// try keys (rng1 of every link, the second word pair of each split) stay in registers under compile-time indices, and a
+// survivor at phase-1 slot < tape_cap stores them as key_tape[link][slot]: the survivors of a wave have consecutive
+// slots, so each of the 10 * kTape stores is one coalesced wave store.  Phase 2 reads them instead of walking the chain
+// a second time.  Only the survivors (~25 % of the candidates in the reference's arena) are written.
+constexpr int kTapeObjects = 8; // the reference's hazard count: the one instantiation with a tape
+// the links of the chain, the try key of link K into keys[K]: a pack expansion, so every index is a constant and the
+// keys stay in registers (`#pragma unroll` on a loop of 80 links exceeds the unroller's threshold: the array went to
+// scratch).  The empty asm pins each key in its two VGPRs where it is computed: otherwise the compiler sinks the last
+// Threefry additions into the survivors' store branch and keeps their inputs live instead -- twice the registers, spilled.
+GX_D void pin_vgprs(uint32_t& a, uint32_t& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+template <size_t N, size_t... K>
+GX_D void walk_keep_keys(uint32_t& r0, uint32_t& r1, uint2 (&keys)[N], std::index_sequence<K...>)
+{
+    uint32_t n0, n1, g0, g1;
+    ((split2(r0, r1, n0, n1, g0, g1), r0 = n0, r1 = n1, pin_vgprs(g0, g1),
+      keys[K] = make_uint2(g0, g1)), ...);
+}
+template <int BLOCK, int kTape>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
+void sample_phase1_kernel(SampleParams sp, const int* __restrict__ n_surv0, const uint32_t* __restrict__ surv0,
+                          int* __restrict__ n_surv, uint32_t* __restrict__ surv, uint2* __restrict__ key_tape, int tape_cap)
 {
     const int tid = threadIdx.x;
     const int S0 = *n_surv0;
@@ -128,7 +146,12 @@ __global__ __launch_bounds__(BLOCK) void sample_phase1_kernel(SampleParams sp,
         const float gx = u2f(h0.w), gy = u2f(h1.x);
         const uint32_t s0 = r0, s1 = r1; // chain state after the goal
         uint32_t n0, n1, g0 = 0, g1 = 0;
-        for (int t = 0; t < nh; ++t) { split2(r0, r1, n0, n1, g0, g1); r0 = n0; r1 = n1; }
+        uint2 keys[kTape > 0 ? 10 * kTape : 1];
+        if (kTape > 0) {
+            walk_keep_keys(r0, r1, keys, std::make_index_sequence<10 * kTape>{});
+        } else {
+            for (int t = 0; t < nh; ++t) { split2(r0, r1, n0, n1, g0, g1); r0 = n0; r1 = n1; }
+        }
         float rx[10], ry[10];
         bool any_far = false;
 #pragma unroll
@@ -143,6 +166,10 @@ __global__ __launch_bounds__(BLOCK) void sample_phase1_kernel(SampleParams sp,
             rec[0] = (uint32_t)j; rec[1] = s0; rec[2] = s1; rec[3] = f2u(gx); rec[4] = f2u(gy);
 #pragma unroll
             for (int t = 0; t < 10; ++t) { rec[5 + 2 * t] = f2u(rx[t]); rec[6 + 2 * t] = f2u(ry[t]); }
+            if (kTape > 0 && slot < tape_cap) {
+#pragma unroll
+                for (int t = 0; t < 10 * kTape; ++t) key_tape[(size_t)t * tape_cap + slot] = keys[t];
+            }
         }
     }
 }
@@ -196,7 +223,9 @@ __global__ __launch_bounds__(kP2Block * kP2Waves) void sample_phase2_kernel(Samp
                                                                  const uint32_t* __restrict__ surv,
                                                                  uint8_t* __restrict__ ok,
                                                                  float2* __restrict__ cand_xy,
-                                                                 int* __restrict__ blk_cnt)
+                                                                 int* __restrict__ blk_cnt,
+                                                                 const uint2* __restrict__ key_tape,
+                                                                 int tape_cap)
 {
     extern __shared__ float4 smem4[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -247,6 +276,17 @@ __global__ __launch_bounds__(kP2Block * kP2Waves) void sample_phase2_kernel(Samp
             }
         }
         if (!(rvalid & rfar)) alive = false;
+        // the objects' try keys: from phase 1's key tape when every survivor of this wave has an entry (wave-uniform),
+        // otherwise from the chain, walked again from the state after the goal.  The next object's keys are requested
+        // before this object's rounds.  (A double-buffered form that keeps them in flight through the rounds needs 136
+        // VGPRs, 3 waves per SIMD instead of 4, and made the epoch slower.)
+        const bool from_tape = !kFused && key_tape && (base + kP2Block < NS ? base + kP2Block : NS) <= tape_cap;
+        const uint2* tape_col = key_tape + (live ? i : base);
+        uint2 nk[10];
+        if (from_tape) {
+#pragma unroll
+            for (int t = 0; t < 10; ++t) nk[t] = tape_col[(size_t)t * tape_cap];
+        }
         for (int o = 1; o < nobj - 1; ++o) { // hazards, then pillars
             const int tn = o <= sp.H ? 1 : 3;
             const float4 hb = sp.haz_bounds ? sp.haz_bounds[o - 1]
@@ -254,12 +294,25 @@ __global__ __launch_bounds__(kP2Block * kP2Waves) void sample_phase2_kernel(Samp
             // cutoffs against a placed goal / hazard / pillar (in registers: no scalar loads in the loops below)
             const float tg = sp.thr_sq[0][tn], th = sp.thr_sq[1][tn], tp = sp.thr_sq[3][tn];
             uint32_t k9a = 0, k9b = 0;
+            if (from_tape) {
+                uint2 ck[10];
 #pragma unroll
-            for (int t = 0; t < 10; ++t) {
-                uint32_t n0, n1, g0, g1;
-                split2(r0, r1, n0, n1, g0, g1); r0 = n0; r1 = n1;
-                if (t < 9) S.keys[t][lane] = make_uint2(g0, g1);
-                else { k9a = g0; k9b = g1; }
+                for (int t = 0; t < 10; ++t) ck[t] = nk[t];
+                if (o + 1 < nobj - 1) {
+#pragma unroll
+                    for (int t = 0; t < 10; ++t) nk[t] = tape_col[(size_t)(10 * o + t) * tape_cap];
+                }
+#pragma unroll
+                for (int t = 0; t < 9; ++t) S.keys[t][lane] = ck[t];
+                k9a = ck[9].x; k9b = ck[9].y;
+            } else {
+#pragma unroll
+                for (int t = 0; t < 10; ++t) {
+                    uint32_t n0, n1, g0, g1;
+                    split2(r0, r1, n0, n1, g0, g1); r0 = n0; r1 = n1;
+                    if (t < 9) S.keys[t][lane] = make_uint2(g0, g1);
+                    else { k9a = g0; k9b = g1; }
+                }
             }
             bool conflicted = alive;
             float px = -__builtin_inff(), py = -__builtin_inff();
@@ -554,9 +607,14 @@ hipError_t launch_sample(const SampleParams& sp, const Pool& pl, hipStream_t s, 
     if (const char* ev = getenv("GX_SAMPLE_GRID_CAP")) cap = atoi(ev) > 0 ? atoi(ev) : cap;
     const int grid1 = grid < (cap < 3072 ? cap : 3072) ? grid : (cap < 3072 ? cap : 3072);
     const bool fused = sp.fused != 0; // sparse arena: one walk of the chain (sample_phase2_kernel<true>), no phase 1
-    if (!fused)
-        hipLaunchKernelGGL(sample_phase1_kernel<kSampleBlock>, dim3(grid1), dim3(kSampleBlock), 0, s, sp, pl.n_surv + 1,
-                           pl.surv0, pl.n_surv, pl.surv);
+    // the key tape: this object count has the instantiation, and the pool has a tape (results do not depend on either)
+    uint2* const tape = sample_tape_objects(sp) && pl.key_tape ? pl.key_tape : nullptr;
+    if (tape)
+        hipLaunchKernelGGL((sample_phase1_kernel<kSampleBlock, kTapeObjects>), dim3(grid1), dim3(kSampleBlock), 0, s, sp,
+                           pl.n_surv + 1, pl.surv0, pl.n_surv, pl.surv, tape, pl.tape_cap);
+    else if (!fused)
+        hipLaunchKernelGGL((sample_phase1_kernel<kSampleBlock, 0>), dim3(grid1), dim3(kSampleBlock), 0, s, sp, pl.n_surv + 1,
+                           pl.surv0, pl.n_surv, pl.surv, nullptr, 0);
     if (after_phase1) {
         const hipError_t st = hipEventRecord(after_phase1, s);
         if (st != hipSuccess) return st;
@@ -569,16 +627,18 @@ hipError_t launch_sample(const SampleParams& sp, const Pool& pl, hipStream_t s, 
     const size_t lds2 = wpb * lds_wave;
     if (fused)
         hipLaunchKernelGGL(sample_phase2_kernel<true>, dim3(grid2), dim3(kP2Block * wpb), lds2, s, sp, pl.n_surv + 1, pl.surv0,
-                           pl.cand_ok, pl.cand_xy, pl.blk_cnt);
+                           pl.cand_ok, pl.cand_xy, pl.blk_cnt, nullptr, 0);
     else
         hipLaunchKernelGGL(sample_phase2_kernel<false>, dim3(grid2), dim3(kP2Block * wpb), lds2, s, sp, pl.n_surv, pl.surv,
-                           pl.cand_ok, pl.cand_xy, pl.blk_cnt);
+                           pl.cand_ok, pl.cand_xy, pl.blk_cnt, tape, tape ? pl.tape_cap : 0);
     hipLaunchKernelGGL(scan_compact_kernel, dim3((M + kCompactTile - 1) / kCompactTile), dim3(kSampleBlock), 0, s, M,
                        pl.cand_ok, pl.blk_cnt, pl.cand_of, pl.layout_size, pl.n_surv);
     return hipSuccess;
 }
 
 int sample_compact_tile() { return kCompactTile; }
+
+int sample_tape_objects(const SampleParams& sp) { return !sp.fused && sp.nobj_total - 2 == kTapeObjects ? kTapeObjects : 0; }
 
 
 #define GX_ROBOT_DISPATCH(CALL)                                              \
