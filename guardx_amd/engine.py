@@ -773,21 +773,36 @@ class Engine:
     def pack_actor_critic(ac=None, *, mu_net=None, v_net=None, log_std=None, device=None):
         """Flatten MLPActorCritic(hidden_sizes=(h, h), tanh) weights (trpo_core.py:110-164; h = 64 is the reference
         default, trpo.py:606-607 --hid / --l) into the layout gx_rollout_policy expects.  `ac` needs .pi.mu_net,
-        .pi.log_std, .v.v_net (nn.Sequential of Linear/Tanh/Linear/Tanh/Linear[/Identity]); or pass the three pieces."""
+        .pi.log_std, .v.v_net (nn.Sequential of Linear/Tanh/Linear/Tanh/Linear[/Identity]); or pass the three pieces.
+        Anything the kernels would evaluate differently (another activation, an output activation, a log_std or an
+        input width that does not match) raises NotImplementedError."""
         if ac is not None:
             mu_net, v_net, log_std = ac.pi.mu_net, ac.v.v_net, ac.pi.log_std
-        parts, widths = [], set()
+        parts, widths, lins = [], set(), []
         for net in (mu_net, v_net):
-            lin = [m for m in net if isinstance(m, torch.nn.Linear)]
-            if len(lin) != 3 or lin[0].out_features != lin[1].out_features or lin[1].in_features != lin[0].out_features:
+            mods = [m for m in net if not isinstance(m, torch.nn.Identity)]
+            lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
+            if len(lin) != 3 or lin[0].out_features != lin[1].out_features or lin[1].in_features != lin[0].out_features \
+                    or lin[2].in_features != lin[1].out_features:
                 raise NotImplementedError("rollout_policy supports two hidden layers of equal width (--l 2)")
+            if [type(m) for m in mods] != [torch.nn.Linear, torch.nn.Tanh] * 2 + [torch.nn.Linear]:
+                raise NotImplementedError("rollout_policy supports Tanh hidden activations and a linear output only "
+                                          "(activation=nn.Tanh, output_activation=nn.Identity)")
             widths.add(lin[0].out_features)
+            lins.append(lin)
             for m in lin:
                 parts += [m.weight.detach().reshape(-1), m.bias.detach().reshape(-1)]
         if len(widths) != 1 or widths.pop() not in Engine.POLICY_HIDDEN:
             raise NotImplementedError(f"rollout_policy supports hidden_sizes (h, h) with h in {Engine.POLICY_HIDDEN}, "
                                       "the same for actor and critic")
-        parts.append(torch.as_tensor(log_std).detach().reshape(-1))
+        if lins[0][0].in_features != lins[1][0].in_features:
+            raise NotImplementedError("rollout_policy needs the actor and the critic to read the same observation width")
+        if lins[1][2].out_features != 1:
+            raise NotImplementedError("rollout_policy supports a critic with one output")
+        log_std = torch.as_tensor(log_std).detach().reshape(-1)
+        if log_std.numel() != lins[0][2].out_features:
+            raise NotImplementedError(f"log_std has {log_std.numel()} entries, mu_net {lins[0][2].out_features} outputs")
+        parts.append(log_std)
         flat = torch.cat([t.to(torch.float32) for t in parts])
         return flat.to(device) if device is not None else flat
 
