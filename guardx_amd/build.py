@@ -1,4 +1,4 @@
-"""Build libguardx_hip.so and libguardx_critic.so (gfx950) in-tree with hipcc.
+"""Build libguardx_hip.so, libguardx_critic.so and libguardx_statewise.so (gfx950) in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -69,6 +69,12 @@ CRITIC_SOURCES = ["gx_critic.hip"]
 CRITIC_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_critic.h")]
 CRITIC_BUILD_ID_FILE = os.path.join(LIB_DIR, "CRITIC_BUILD_ID")
 
+# The state-wise (SCPO) policy step (include/guardx_statewise.h): a third library on the same terms.
+STATEWISE_LIB = os.path.join(LIB_DIR, "libguardx_statewise.so")
+STATEWISE_SOURCES = ["gx_statewise.hip"]
+STATEWISE_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_statewise.h")]
+STATEWISE_BUILD_ID_FILE = os.path.join(LIB_DIR, "STATEWISE_BUILD_ID")
+
 
 _COMPILER = None
 
@@ -122,6 +128,20 @@ def critic_source_hash():
     return h.hexdigest()[:24]
 
 
+def statewise_source_hash():
+    """source_hash() of libguardx_statewise.so: its sources, every project header they include, FLAGS and the compiler
+    (compiled in as gxs_build_id() and checked at load time, guardx_amd/_statewise_native.py)."""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(compiler_id().encode() + b"\0")
+    for n in sorted(set(STATEWISE_SOURCES) | set(STATEWISE_HEADERS)):
+        h.update(n.encode() + b"\0")
+        with open(os.path.join(CSRC, n), "rb") as f:
+            h.update(f.read())
+    h.update(repr(FLAGS).encode())
+    return h.hexdigest()[:24]
+
+
 def _obj(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
 
@@ -150,6 +170,18 @@ def critic_needs_build():
     return not os.path.exists(CRITIC_LIB) or built_critic_id() != critic_source_hash()
 
 
+def built_statewise_id():
+    try:
+        with open(STATEWISE_BUILD_ID_FILE) as f:
+            return f.read().strip()
+    except OSError:
+        return None
+
+
+def statewise_needs_build():
+    return not os.path.exists(STATEWISE_LIB) or built_statewise_id() != statewise_source_hash()
+
+
 def _dep_hash(src):
     """identity of one object file: its source, every header, its flags (objects are reused across builds)"""
     import hashlib
@@ -163,7 +195,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  Both libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All three libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)
@@ -174,6 +206,8 @@ def build(force=False, verbose=False, jobs=None):
                 _build_locked(force, verbose, jobs)
             if force or critic_needs_build():
                 _build_critic_locked(verbose)
+            if force or statewise_needs_build():
+                _build_statewise_locked(verbose)
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -233,7 +267,24 @@ def _build_critic_locked(verbose):
     return CRITIC_LIB
 
 
+def _build_statewise_locked(verbose):
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    bid = statewise_source_hash()
+    tmp = STATEWISE_LIB + ".tmp.%d" % os.getpid()
+    cmd = [hipcc] + FLAGS + ['-DGXS_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
+          [os.path.join(CSRC, s) for s in STATEWISE_SOURCES]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, STATEWISE_LIB)
+    with open(STATEWISE_BUILD_ID_FILE + ".tmp", "w") as f:
+        f.write(bid + "\n")
+    os.replace(STATEWISE_BUILD_ID_FILE + ".tmp", STATEWISE_BUILD_ID_FILE)
+    return STATEWISE_LIB
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
     print("critic build id", built_critic_id())
+    print("statewise build id", built_statewise_id())

@@ -332,6 +332,7 @@ class Engine:
         self._spec = C.c_int32(0)
         self._spec_ref = C.byref(self._spec)
         self._rd_obs = None          # what reset_done() returns for the step just made (speculated in-kernel)
+        self._statewise = None       # rollout_statewise's M / first / step counter (guardx_amd/statewise.py), made on first use
         self._obs = None
         self._reward = None
         self._done = None
@@ -478,6 +479,8 @@ class Engine:
         obs = self._new(self.env_num, self.obs_flat_size)
         _native.check(self._lib.gx_reset(self._h, obs.data_ptr(), self._stream()))
         self._rd_obs = None
+        if self._statewise is not None:
+            self._statewise.reset()     # M = 0, first = 1 (scpo.py:637-639, 697-699)
         if not check:
             self._obs = obs
             return obs
@@ -811,12 +814,25 @@ class Engine:
         return 2 * (h * D + h + h * h + h) + (A + 1) * h + (A + 1) + A
 
     @staticmethod
-    def pack_critic(critic, device=None):
+    def pack_critic(critic, device=None, *, output='identity'):
         """Flatten a cost critic (`ac.vc` of the CPO-family cores, safe_rl_libX/cpo/cpo_core.py: anything with .v_net,
         or the nn.Sequential Linear/Tanh/Linear/Tanh/Linear[/Identity] itself) into the layout of
-        guardx_amd.critic.critic_values and rollout_policy(..., cost_critic=): W1 b1 W2 b2 W3 b3, float32."""
+        guardx_amd.critic.critic_values and rollout_policy(..., cost_critic=): W1 b1 W2 b2 W3 b3, float32.
+        output='softplus': SCPO's MLPMaxCostCritic (scpo_core.py:158-166), the same layers followed by nn.Softplus
+        (beta 1, threshold 20), for rollout_statewise(..., cost_critic=).  The layout is the same; the returned tensor
+        carries the declaration (guardx_amd.statewise.critic_output), and each rollout refuses the other kind."""
+        from . import statewise as _sw
+        if output not in ('identity', 'softplus'):
+            raise ValueError(f"pack_critic: output must be 'identity' or 'softplus', got {output!r}")
         net = getattr(critic, 'v_net', critic)
         mods = [m for m in net if not isinstance(m, torch.nn.Identity)]
+        if output == 'softplus':
+            last = mods[-1] if mods else None
+            if not isinstance(last, torch.nn.Softplus):
+                raise NotImplementedError("pack_critic(output='softplus') needs a critic whose last module is nn.Softplus")
+            if last.beta != 1 or last.threshold != 20:
+                raise NotImplementedError("pack_critic(output='softplus') supports nn.Softplus(beta=1, threshold=20)")
+            mods = mods[:-1]
         lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
         if len(lin) != 3:
             raise NotImplementedError("the cost critic pass supports two hidden layers (--l 2)")
@@ -830,7 +846,21 @@ class Engine:
         if lin[2].out_features != 1:
             raise NotImplementedError("the cost critic pass supports one output")
         flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for m in lin for t in (m.weight, m.bias)])
-        return flat.to(device) if device is not None else flat
+        flat = flat.to(device) if device is not None else flat
+        setattr(flat, _sw.OUTPUT_ATTR, output)
+        return flat
+
+    def rollout_statewise(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
+        """T x (M update -> ac.step(cat(obs, M)) -> env.step -> reset_done) on device: SCPO's collection loop
+        (scpo.py:640-720).  `params` = pack_actor_critic(ac) of an actor-critic built on obs_dim + 1 inputs,
+        `cost_critic` = pack_critic(ac.vc, output='softplus').  Two launches per control step (guardx_amd/statewise.py).
+        Returns a dict of time-major tensors: obs (T,N,D+1) [what the networks saw: the env's row and M], act, mu
+        (T,N,A), logp, val, vc, rew, cost [the env's raw cost], cost_inc [max(cost - M, 0), the whole cost on an
+        episode's first step], M [the running maximum after step t, before any reset], done (T,N), plus obs_last
+        (N,D+1), val_last, vc_last (N,), logstd (A,).  M and the first-step flag persist across calls; reset() clears
+        them.  The noise counter is this path's own (0 at construction, + T per call)."""
+        from . import statewise as _sw
+        return _sw.rollout(self, params, T, cost_critic, obs0, noise_seed)
 
     def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of
@@ -856,6 +886,9 @@ class Engine:
                              f"{[self._policy_floats(D, A, h) for h in self.POLICY_HIDDEN]} (hidden {self.POLICY_HIDDEN})")
         if cost_critic is not None:
             from . import critic as _critic
+            if getattr(cost_critic, 'gx_output', None) == 'softplus':
+                raise ValueError("rollout_policy evaluates the cost critic with a linear output; cost_critic was packed "
+                                 "with output='softplus' (SCPO's MLPMaxCostCritic: use rollout_statewise)")
             cost_critic = cost_critic.to(device=self.device, dtype=torch.float32).contiguous()
             if _critic.critic_hidden(D, cost_critic.numel()) is None:
                 raise ValueError(f"cost_critic has {cost_critic.numel()} floats; expected one of "

@@ -168,3 +168,40 @@ def cost_rollout_batch(out, gamma=0.99, lam=0.95):
                 cost_ret=env_major(cost_ret).view(N * T), adc=adc.view(N * T),
                 logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
                 logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous())
+
+
+def statewise_rollout_batch(out, gamma=0.99, lam=0.95, cgamma=1.0, clam=0.95, cost_signal='increment', bootstrap=False):
+    """An Engine.rollout_statewise result as the batch SCPOBufferX.get() returns after SCPO's collection loop
+    (safe_rl_libX/scpo/scpo.py:30-175, 640-720): store() every step, finish_path() with v = vc = 0 for the envs done at
+    that step, a closing finish_path() at the time-out.  The cost channel runs with SCPO's own cgamma / clam
+    (scpo.py:36: no discount of the cost).  Env-major, flattened: obs act ret adv cost_ret adc logp mu logstd; adv
+    normalised per env, adc centred per env only (scpo.py:148-160).
+    cost_signal: 'increment' = out['cost_inc'], the max(cost - M, 0) SCPO defines; 'reference' = out['M']: what
+    scpo.py:647-654 stores as written (its `cost_increase` and `M_next` are the same tensor, which ends up holding M_next).
+    bootstrap: False closes every path at step T - 1 with 0, as SCPO's time-out does (scpo.py:683-686); True bootstraps
+    the envs not done at step T - 1 with val_last / vc_last (a call shorter than the episode)."""
+    if cost_signal not in ('increment', 'reference'):
+        raise ValueError(f"cost_signal must be 'increment' or 'reference', got {cost_signal!r}")
+    for k in ('vc', 'rew', 'val', 'cost_inc', 'M', 'done', 'obs', 'val_last', 'vc_last'):
+        if k not in out:
+            raise KeyError(f"statewise_rollout_batch needs out['{k}'] (Engine.rollout_statewise)")
+    T, N = out['rew'].shape
+    costs = out['cost_inc'] if cost_signal == 'increment' else out['M']
+    lv, lvc = None, None
+    if bootstrap:
+        alive = 1.0 - out['done'][-1]
+        lv, lvc = out['val_last'] * alive, out['vc_last'] * alive
+    adv, ret = gae_rollout(out['rew'], out['val'], out['done'], lv, gamma, lam)
+    adc, cost_ret = gae_rollout(costs, out['vc'], out['done'], lvc, cgamma, clam)
+    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
+    adv, adc = env_major(adv), env_major(adc)
+    lib = _native.load()
+    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))
+    _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1, stream))
+    _native.check(lib.gx_adv_normalize(N, T, adc.data_ptr(), 0, stream))
+    A = out['act'].shape[-1]
+    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
+                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
+                cost_ret=env_major(cost_ret).view(N * T), adc=adc.view(N * T),
+                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
+                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous())
