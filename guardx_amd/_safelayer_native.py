@@ -1,0 +1,82 @@
+"""ctypes binding of libguardx_safelayer.so (include/guardx_safelayer.h): the safety-layer policy step.
+
+Like _native, _critic_native and _statewise_native, there is no CPU fallback: a missing library is built in place with
+hipcc, and a library built from other sources than the tree's is refused.
+"""
+import ctypes as C
+import os
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "lib", "libguardx_safelayer.so")
+
+GXL_OK, GXL_ERR_ARG, GXL_ERR_UNSUPPORTED, GXL_ERR_HIP = 0, 1, 2, 4
+
+_FP = C.c_void_p  # device pointers travel as integers
+
+
+class GxlStepArgs(C.Structure):
+    """gxl_step_args, field for field"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("N", C.c_int32), ("D", C.c_int32), ("A", C.c_int32),
+        ("hidden", C.c_int32), ("g_hidden", C.c_int32), ("env_offset", C.c_int32), ("T", C.c_int32), ("t", C.c_int32),
+        ("correct", C.c_int32), ("seed", C.c_uint32 * 2), ("step0", C.c_uint32), ("delta", C.c_float),
+        ("d_params", _FP), ("d_g_params", _FP), ("d_work", _FP), ("d_obs0", _FP), ("d_obs_rd", _FP),
+        ("d_rew_in", _FP), ("d_cost_in", _FP), ("d_done_in", _FP), ("d_prev_c", _FP),
+        ("d_obs", _FP), ("d_act", _FP), ("d_act_safe", _FP), ("d_mu", _FP), ("d_g", _FP), ("d_logp", _FP),
+        ("d_val", _FP), ("d_rew", _FP), ("d_cost", _FP), ("d_done", _FP), ("d_prev_cost", _FP),
+        ("d_obs_last", _FP), ("d_val_last", _FP), ("d_logstd", _FP),
+    ]
+
+
+# every symbol include/guardx_safelayer.h declares: name -> (restype, argtypes)
+SYMBOLS = {
+    "gxl_last_error": (C.c_char_p, []),
+    "gxl_build_id": (C.c_char_p, []),
+    "gxl_params_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gxl_g_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gxl_work_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gxl_prepare": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_void_p]),
+    "gxl_policy_step": (C.c_int, [C.POINTER(GxlStepArgs), C.c_void_p]),
+    "gxl_correction_probe": (C.c_int, [C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_float, _FP, C.c_void_p]),
+}
+
+_lib = None
+
+
+def load():
+    """Load libguardx_safelayer.so; raises (never falls back) when it is unavailable or was built from other sources."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    from . import build as _build
+    want = _build.safelayer_source_hash()
+    if _build.safelayer_needs_build():
+        try:
+            _build.build(force=False)
+        except Exception as exc:  # noqa: BLE001
+            raise ImportError(
+                f"{LIB_PATH} is missing or stale (sources {want}, library {_build.built_safelayer_id()}) and could not "
+                f"be built with hipcc ({exc}); run `python -m guardx_amd.build`") from exc
+    lib = C.CDLL(LIB_PATH)
+    for name, (res, args) in SYMBOLS.items():
+        fn = getattr(lib, name)  # AttributeError if the ABI drifted
+        fn.restype = res
+        fn.argtypes = args
+    got = lib.gxl_build_id().decode()
+    if got != want:
+        raise ImportError(f"{LIB_PATH} was built from other sources (library {got}, tree {want}); "
+                          "run `python -m guardx_amd.build`")
+    _lib = lib
+    return lib
+
+
+class GxlError(RuntimeError):
+    def __init__(self, status, msg):
+        super().__init__(f"guardx safelayer status {status}: {msg}")
+        self.status = status
+
+
+def check(status):
+    if status != GXL_OK:
+        msg = load().gxl_last_error()
+        raise GxlError(status, msg.decode() if msg else "")

@@ -1,4 +1,5 @@
-"""Build libguardx_hip.so, libguardx_critic.so and libguardx_statewise.so (gfx950) in-tree with hipcc.
+"""Build libguardx_hip.so, libguardx_critic.so, libguardx_statewise.so and libguardx_safelayer.so (gfx950) in-tree with
+hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -75,6 +76,12 @@ STATEWISE_SOURCES = ["gx_statewise.hip"]
 STATEWISE_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_statewise.h")]
 STATEWISE_BUILD_ID_FILE = os.path.join(LIB_DIR, "STATEWISE_BUILD_ID")
 
+# The safety-layer policy step (include/guardx_safelayer.h): a fourth library on the same terms.
+SAFELAYER_LIB = os.path.join(LIB_DIR, "libguardx_safelayer.so")
+SAFELAYER_SOURCES = ["gx_safelayer.hip"]
+SAFELAYER_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_safelayer.h")]
+SAFELAYER_BUILD_ID_FILE = os.path.join(LIB_DIR, "SAFELAYER_BUILD_ID")
+
 
 _COMPILER = None
 
@@ -142,6 +149,20 @@ def statewise_source_hash():
     return h.hexdigest()[:24]
 
 
+def safelayer_source_hash():
+    """source_hash() of libguardx_safelayer.so: its sources, every project header they include, FLAGS and the compiler
+    (compiled in as gxl_build_id() and checked at load time, guardx_amd/_safelayer_native.py)."""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(compiler_id().encode() + b"\0")
+    for n in sorted(set(SAFELAYER_SOURCES) | set(SAFELAYER_HEADERS)):
+        h.update(n.encode() + b"\0")
+        with open(os.path.join(CSRC, n), "rb") as f:
+            h.update(f.read())
+    h.update(repr(FLAGS).encode())
+    return h.hexdigest()[:24]
+
+
 def _obj(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
 
@@ -182,6 +203,18 @@ def statewise_needs_build():
     return not os.path.exists(STATEWISE_LIB) or built_statewise_id() != statewise_source_hash()
 
 
+def built_safelayer_id():
+    try:
+        with open(SAFELAYER_BUILD_ID_FILE) as f:
+            return f.read().strip()
+    except OSError:
+        return None
+
+
+def safelayer_needs_build():
+    return not os.path.exists(SAFELAYER_LIB) or built_safelayer_id() != safelayer_source_hash()
+
+
 def _dep_hash(src):
     """identity of one object file: its source, every header, its flags (objects are reused across builds)"""
     import hashlib
@@ -195,7 +228,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All three libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All four libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)
@@ -208,6 +241,8 @@ def build(force=False, verbose=False, jobs=None):
                 _build_critic_locked(verbose)
             if force or statewise_needs_build():
                 _build_statewise_locked(verbose)
+            if force or safelayer_needs_build():
+                _build_safelayer_locked(verbose)
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -283,8 +318,25 @@ def _build_statewise_locked(verbose):
     return STATEWISE_LIB
 
 
+def _build_safelayer_locked(verbose):
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    bid = safelayer_source_hash()
+    tmp = SAFELAYER_LIB + ".tmp.%d" % os.getpid()
+    cmd = [hipcc] + FLAGS + ['-DGXL_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
+          [os.path.join(CSRC, s) for s in SAFELAYER_SOURCES]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, SAFELAYER_LIB)
+    with open(SAFELAYER_BUILD_ID_FILE + ".tmp", "w") as f:
+        f.write(bid + "\n")
+    os.replace(SAFELAYER_BUILD_ID_FILE + ".tmp", SAFELAYER_BUILD_ID_FILE)
+    return SAFELAYER_LIB
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
     print("critic build id", built_critic_id())
     print("statewise build id", built_statewise_id())
+    print("safelayer build id", built_safelayer_id())

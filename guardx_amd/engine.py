@@ -333,6 +333,7 @@ class Engine:
         self._spec_ref = C.byref(self._spec)
         self._rd_obs = None          # what reset_done() returns for the step just made (speculated in-kernel)
         self._statewise = None       # rollout_statewise's M / first / step counter (guardx_amd/statewise.py), made on first use
+        self._safelayer = None       # rollout_safelayer's prev_c / step counter (guardx_amd/safelayer.py), made on first use
         self._obs = None
         self._reward = None
         self._done = None
@@ -481,6 +482,8 @@ class Engine:
         self._rd_obs = None
         if self._statewise is not None:
             self._statewise.reset()     # M = 0, first = 1 (scpo.py:637-639, 697-699)
+        if self._safelayer is not None:
+            self._safelayer.reset()     # prev_c = 0 (safelayer.py:507, 567)
         if not check:
             self._obs = obs
             return obs
@@ -861,6 +864,35 @@ class Engine:
         them.  The noise counter is this path's own (0 at construction, + T per call)."""
         from . import statewise as _sw
         return _sw.rollout(self, params, T, cost_critic, obs0, noise_seed)
+
+    @staticmethod
+    def pack_g_net(ccritic, device=None, *, act_dim=None):
+        """Flatten the safety layer's g_net (`ac.ccritic` of safelayer_core.py:147-156: anything with .g_net, or the
+        nn.Sequential Linear/Tanh/Linear/Tanh/Linear[/Identity] itself, output width A) for rollout_safelayer(g_net=):
+        W1 b1 W2 b2 W3 b3, float32; its hidden width may differ from the actor's.  Anything the kernel would evaluate
+        differently (another activation, an output activation, unequal hidden layers, an output width that is odd,
+        above 16 or not `act_dim` when that is given) raises NotImplementedError."""
+        from . import safelayer as _sl
+        flat = _sl.pack_g_net(ccritic, device)
+        if act_dim is not None and getattr(flat, _sl.G_NET_ATTR) != int(act_dim):
+            raise NotImplementedError(f"g_net has {getattr(flat, _sl.G_NET_ATTR)} outputs; the action has {int(act_dim)}")
+        return flat
+
+    def rollout_safelayer(self, params, T, obs0=None, noise_seed=(0, 0), *, g_net, correct=True, delta=0.0):
+        """T x (ac.step -> safety correction -> env.step(act_safe) -> reset_done) on device: the safelayer learner's
+        collection loop (safelayer.py:514-581; Dalal et al. 2018).  `params` = pack_actor_critic(ac), `g_net` =
+        pack_g_net(ac.ccritic).  With g = g_net(obs) and pred = g.a + prev_c: act_safe = a where pred <= delta, else
+        clamp(a - relu((pred - delta) / (g.g + 1e-8)) g, -1, 1) (include/guardx_safelayer.h fixes the order of
+        operations).  correct=False is the learner's warm-up branch: act_safe = act; g and prev_cost are still returned.
+        Two launches per control step (guardx_amd/safelayer.py).
+        Returns a dict of time-major tensors: obs (T,N,D), act [the actor's sample; logp is its log-probability],
+        act_safe [what env.step received], mu, g (T,N,A), logp, val, rew, cost, prev_cost [the prev_c the correction at
+        step t used], done (T,N), plus obs_last (N,D), val_last (N,), logstd (A,).  prev_c (the cost of the env's
+        previous step, 0 after a done) persists across calls; reset() clears it; step(), rollout_policy and
+        rollout_statewise neither read nor write it.  The noise counter is this path's own (0 at construction, + T per
+        call)."""
+        from . import safelayer as _sl
+        return _sl.rollout(self, params, T, g_net, obs0, noise_seed, correct, delta)
 
     def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of

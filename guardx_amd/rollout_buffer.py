@@ -205,3 +205,51 @@ def statewise_rollout_batch(out, gamma=0.99, lam=0.95, cgamma=1.0, clam=0.95, co
                 cost_ret=env_major(cost_ret).view(N * T), adc=adc.view(N * T),
                 logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
                 logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous())
+
+
+def _gae_host(rew, val, done, gamma, lam):
+    """gae_rollout + the per-env normalisation for HOST tensors, in plain torch: the same recursion the kernels run
+    (paths closed with 0 at every done step and at step T - 1).  Returns (adv normalised, env-major (N, T); ret (T, N))."""
+    T, N = rew.shape
+    adv, ret = torch.empty_like(rew), torch.empty_like(rew)
+    a_next, r_next, v_next = torch.zeros(N), torch.zeros(N), torch.zeros(N)
+    for t in range(T - 1, -1, -1):
+        live = 1.0 - (done[t] > 0).to(torch.float32) if t + 1 < T else torch.zeros(N)
+        delta = rew[t] + gamma * live * v_next - val[t]
+        a_next = delta + gamma * lam * live * a_next
+        r_next = rew[t] + gamma * live * r_next
+        adv[t], ret[t], v_next = a_next, r_next, val[t]
+    adv = adv.transpose(0, 1).contiguous()
+    mean = adv.sum(1, keepdim=True) / T
+    std = (((adv - mean) ** 2).sum(1, keepdim=True) / T).sqrt()
+    return (adv - mean) / std, ret
+
+
+def safelayer_rollout_batch(out, gamma=0.99, lam=0.95):
+    """An Engine.rollout_safelayer result as the batch SafeLayerBufferX.get() returns after the safelayer learner's
+    collection loop (safe_rl_libX/safelayer/safelayer.py:32-154, 514-583): store() every step, finish_path() with v = 0
+    for the envs done at that step, a closing finish_path() over every env at the time-out, without bootstrap.
+    Env-major, flattened: obs act act_safe ret adv logp mu logstd cost prev_cost; adv normalised per env
+    (safelayer.py:137-141).  Device tensors go through the GAE and normalisation kernels; a dict of host tensors (a
+    result moved to the CPU) is served by the same recursion in torch."""
+    for k in ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'prev_cost', 'done'):
+        if k not in out:
+            raise KeyError(f"safelayer_rollout_batch needs out['{k}'] (Engine.rollout_safelayer)")
+    T, N = out['rew'].shape
+    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
+    if out['rew'].is_cuda:
+        adv, ret = gae_rollout(out['rew'], out['val'], out['done'], None, gamma, lam)
+        adv = env_major(adv)
+        lib = _native.load()
+        _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1,
+                                           C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))))
+    else:
+        f = lambda x: x.to(torch.float32)   # noqa: E731
+        adv, ret = _gae_host(f(out['rew']), f(out['val']), f(out['done']), float(gamma), float(lam))
+    A = out['act'].shape[-1]
+    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
+                act_safe=env_major(out['act_safe']).view(N * T, -1),
+                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
+                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
+                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous(),
+                cost=env_major(out['cost']).view(N * T), prev_cost=env_major(out['prev_cost']).view(N * T))
