@@ -1,5 +1,5 @@
-"""Build libguardx_hip.so, libguardx_critic.so, libguardx_statewise.so and libguardx_safelayer.so (gfx950) in-tree with
-hipcc.
+"""Build libguardx_hip.so, libguardx_critic.so, libguardx_statewise.so, libguardx_safelayer.so and libguardx_usl.so
+(gfx950) in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -82,6 +82,12 @@ SAFELAYER_SOURCES = ["gx_safelayer.hip"]
 SAFELAYER_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_safelayer.h")]
 SAFELAYER_BUILD_ID_FILE = os.path.join(LIB_DIR, "SAFELAYER_BUILD_ID")
 
+# The USL policy step with its gradient-descent correction (include/guardx_usl.h): a fifth library on the same terms.
+USL_LIB = os.path.join(LIB_DIR, "libguardx_usl.so")
+USL_SOURCES = ["gx_usl.hip"]
+USL_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_usl.h")]
+USL_BUILD_ID_FILE = os.path.join(LIB_DIR, "USL_BUILD_ID")
+
 
 _COMPILER = None
 
@@ -163,6 +169,20 @@ def safelayer_source_hash():
     return h.hexdigest()[:24]
 
 
+def usl_source_hash():
+    """source_hash() of libguardx_usl.so: its sources, every project header they include, FLAGS and the compiler
+    (compiled in as gxu_build_id() and checked at load time, guardx_amd/_usl_native.py)."""
+    import hashlib
+    h = hashlib.sha256()
+    h.update(compiler_id().encode() + b"\0")
+    for n in sorted(set(USL_SOURCES) | set(USL_HEADERS)):
+        h.update(n.encode() + b"\0")
+        with open(os.path.join(CSRC, n), "rb") as f:
+            h.update(f.read())
+    h.update(repr(FLAGS).encode())
+    return h.hexdigest()[:24]
+
+
 def _obj(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
 
@@ -215,6 +235,18 @@ def safelayer_needs_build():
     return not os.path.exists(SAFELAYER_LIB) or built_safelayer_id() != safelayer_source_hash()
 
 
+def built_usl_id():
+    try:
+        with open(USL_BUILD_ID_FILE) as f:
+            return f.read().strip()
+    except OSError:
+        return None
+
+
+def usl_needs_build():
+    return not os.path.exists(USL_LIB) or built_usl_id() != usl_source_hash()
+
+
 def _dep_hash(src):
     """identity of one object file: its source, every header, its flags (objects are reused across builds)"""
     import hashlib
@@ -228,7 +260,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All four libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All five libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)
@@ -243,6 +275,8 @@ def build(force=False, verbose=False, jobs=None):
                 _build_statewise_locked(verbose)
             if force or safelayer_needs_build():
                 _build_safelayer_locked(verbose)
+            if force or usl_needs_build():
+                _build_usl_locked(verbose)
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -334,9 +368,26 @@ def _build_safelayer_locked(verbose):
     return SAFELAYER_LIB
 
 
+def _build_usl_locked(verbose):
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    bid = usl_source_hash()
+    tmp = USL_LIB + ".tmp.%d" % os.getpid()
+    cmd = [hipcc] + FLAGS + ['-DGXU_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
+          [os.path.join(CSRC, s) for s in USL_SOURCES]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, USL_LIB)
+    with open(USL_BUILD_ID_FILE + ".tmp", "w") as f:
+        f.write(bid + "\n")
+    os.replace(USL_BUILD_ID_FILE + ".tmp", USL_BUILD_ID_FILE)
+    return USL_LIB
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
     print("critic build id", built_critic_id())
     print("statewise build id", built_statewise_id())
     print("safelayer build id", built_safelayer_id())
+    print("usl build id", built_usl_id())

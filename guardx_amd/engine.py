@@ -334,6 +334,7 @@ class Engine:
         self._rd_obs = None          # what reset_done() returns for the step just made (speculated in-kernel)
         self._statewise = None       # rollout_statewise's M / first / step counter (guardx_amd/statewise.py), made on first use
         self._safelayer = None       # rollout_safelayer's prev_c / step counter (guardx_amd/safelayer.py), made on first use
+        self._usl = None             # rollout_usl's step counter and slab (guardx_amd/usl.py), made on first use
         self._obs = None
         self._reward = None
         self._done = None
@@ -893,6 +894,34 @@ class Engine:
         call)."""
         from . import safelayer as _sl
         return _sl.rollout(self, params, T, g_net, obs0, noise_seed, correct, delta)
+
+    @staticmethod
+    def pack_q_critic(ccritic, device=None):
+        """Flatten USL's cost critic (`ac.ccritic` of usl_core.py:146-151: anything with .c_net, or the nn.Sequential
+        Linear/Tanh/Linear/Tanh/Linear/Softplus itself, on D + A inputs) for rollout_usl(q_critic=): W1 b1 W2 b2 W3 b3,
+        float32; its hidden width may differ from the actor's.  Anything the kernel would evaluate differently (another
+        activation, no Softplus(beta=1, threshold=20) at the end, unequal hidden layers, more than one output) raises
+        NotImplementedError.  The returned tensor carries c_net's input width, which rollout_usl checks against D + A."""
+        from . import usl as _usl
+        return _usl.pack_q_critic(ccritic, device)
+
+    def rollout_usl(self, params, T, obs0=None, noise_seed=(0, 0), *, q_critic, correct=True, delta=0.0, niter=20,
+                    eta=0.05, grad_scale=None):
+        """T x (ac.step -> gradient-descent correction -> env.step(act_safe) -> reset_done) on device: the USL learner's
+        collection loop (usl.py:478-553, usl_core.py:165-196).  `params` = pack_actor_critic(ac), `q_critic` =
+        pack_q_critic(ac.ccritic).  qc = Q(obs, act) on the sampled action; with correct=True, per row and at most niter
+        times: stop if max_k a[k] > 1 (the signed maximum, as the reference writes it) or Q(obs, a) <= delta, else
+        a = a - eta s / (max |s| + 1e-8) with s = grad_scale dQ/da; no clamp (include/guardx_usl.h fixes the order of
+        operations).  grad_scale=None is 1 / env_num, the reference's pred.mean().backward(); 1.0 the unscaled form.
+        correct=False is the learner's warm-up branch: act_safe = act; qc is still returned.
+        Two launches per control step (guardx_amd/usl.py).
+        Returns a dict of time-major tensors: obs (T,N,D), act [the actor's sample; logp is its log-probability],
+        act_safe [what env.step received], mu (T,N,A), logp, val, qc, rew, cost, done (T,N), iters (T,N) [the updates
+        applied, as float32], plus obs_last (N,D), val_last (N,), logstd (A,).  The noise counter is this path's own (0
+        at construction, + T per call, not reset by reset()); step(), reset() and the other rollouts neither read nor
+        advance it."""
+        from . import usl as _usl
+        return _usl.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, niter, eta, grad_scale)
 
     def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of

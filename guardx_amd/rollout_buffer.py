@@ -253,3 +253,38 @@ def safelayer_rollout_batch(out, gamma=0.99, lam=0.95):
                 logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
                 logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous(),
                 cost=env_major(out['cost']).view(N * T), prev_cost=env_major(out['prev_cost']).view(N * T))
+
+
+def usl_rollout_batch(out, gamma=0.99, lam=0.95):
+    """An Engine.rollout_usl result as the batch USLBufferX.get() returns after the USL learner's collection loop
+    (safe_rl_libX/usl/usl.py:50-159, 478-553): store() every step, finish_path() with v = 0 for the envs done at that
+    step, a closing finish_path() over every env at the time-out, without bootstrap.  Env-major, flattened:
+    obs act act_safe ret adv logp mu logstd cost targetc; adv normalised per env (usl.py:142-146);
+    targetc[t] = cost[t] + gamma qc[t + 1] with qc taken as 0 past the end of a path (usl.py:105-107, 125-127): at every
+    done step and at step T - 1.  Device tensors go through the GAE and normalisation kernels; a dict of host tensors (a
+    result moved to the CPU) is served by the same recursion in torch."""
+    for k in ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'qc', 'done'):
+        if k not in out:
+            raise KeyError(f"usl_rollout_batch needs out['{k}'] (Engine.rollout_usl)")
+    T, N = out['rew'].shape
+    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
+    f = lambda x: x.to(torch.float32)   # noqa: E731
+    if out['rew'].is_cuda:
+        adv, ret = gae_rollout(out['rew'], out['val'], out['done'], None, gamma, lam)
+        adv = env_major(adv)
+        lib = _native.load()
+        _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1,
+                                           C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))))
+    else:
+        adv, ret = _gae_host(f(out['rew']), f(out['val']), f(out['done']), float(gamma), float(lam))
+    qc, done = f(out['qc']), f(out['done'])
+    q_next = torch.zeros_like(qc)
+    q_next[:-1] = qc[1:] * (1.0 - (done[:-1] > 0).to(torch.float32))
+    targetc = f(out['cost']) + float(gamma) * q_next
+    A = out['act'].shape[-1]
+    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
+                act_safe=env_major(out['act_safe']).view(N * T, -1),
+                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
+                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
+                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous(),
+                cost=env_major(out['cost']).view(N * T), targetc=env_major(targetc).view(N * T))
