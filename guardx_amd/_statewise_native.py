@@ -1,13 +1,10 @@
 """ctypes binding of libguardx_statewise.so (include/guardx_statewise.h): the state-wise (SCPO) policy step.
 
-Like _native and _critic_native, there is no CPU fallback: a missing library is built in place with hipcc, and a library
-built from other sources than the tree's is refused.
+load / check / GxsError: guardx_amd/_sidelib.py (no CPU fallback; a library built from other sources is refused).
 """
 import ctypes as C
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libguardx_statewise.so")
+from . import _sidelib
 
 GXS_OK, GXS_ERR_ARG, GXS_ERR_UNSUPPORTED, GXS_ERR_HIP = 0, 1, 2, 4
 
@@ -39,43 +36,5 @@ SYMBOLS = {
     "gxs_softplus_probe": (C.c_int, [C.c_int32, _FP, _FP, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load():
-    """Load libguardx_statewise.so; raises (never falls back) when it is unavailable or was built from other sources."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    from . import build as _build
-    want = _build.statewise_source_hash()
-    if _build.statewise_needs_build():
-        try:
-            _build.build(force=False)
-        except Exception as exc:  # noqa: BLE001
-            raise ImportError(
-                f"{LIB_PATH} is missing or stale (sources {want}, library {_build.built_statewise_id()}) and could not "
-                f"be built with hipcc ({exc}); run `python -m guardx_amd.build`") from exc
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the ABI drifted
-        fn.restype = res
-        fn.argtypes = args
-    got = lib.gxs_build_id().decode()
-    if got != want:
-        raise ImportError(f"{LIB_PATH} was built from other sources (library {got}, tree {want}); "
-                          "run `python -m guardx_amd.build`")
-    _lib = lib
-    return lib
-
-
-class GxsError(RuntimeError):
-    def __init__(self, status, msg):
-        super().__init__(f"guardx statewise status {status}: {msg}")
-        self.status = status
-
-
-def check(status):
-    if status != GXS_OK:
-        msg = load().gxs_last_error()
-        raise GxsError(status, msg.decode() if msg else "")
+_side = _sidelib.Binding("statewise", "gxs", SYMBOLS, GXS_OK, "statewise")
+LIB_PATH, load, check, GxsError = _side.path, _side.load, _side.check, _side.Error

@@ -1,13 +1,10 @@
 """ctypes binding of libguardx_usl.so (include/guardx_usl.h): the USL policy step and its correction probe.
 
-Like _native, _critic_native, _statewise_native and _safelayer_native, there is no CPU fallback: a missing library is built in place with
-hipcc, and a library built from other sources than the tree's is refused.
+load / check / GxuError: guardx_amd/_sidelib.py (no CPU fallback; a library built from other sources is refused).
 """
 import ctypes as C
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libguardx_usl.so")
+from . import _sidelib
 
 GXU_OK, GXU_ERR_ARG, GXU_ERR_UNSUPPORTED, GXU_ERR_HIP = 0, 1, 2, 4
 
@@ -43,43 +40,5 @@ SYMBOLS = {
                                        C.c_int32, C.c_float, C.c_float, _FP, _FP, _FP, _FP, _FP, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load():
-    """Load libguardx_usl.so; raises (never falls back) when it is unavailable or was built from other sources."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    from . import build as _build
-    want = _build.usl_source_hash()
-    if _build.usl_needs_build():
-        try:
-            _build.build(force=False)
-        except Exception as exc:  # noqa: BLE001
-            raise ImportError(
-                f"{LIB_PATH} is missing or stale (sources {want}, library {_build.built_usl_id()}) and could not "
-                f"be built with hipcc ({exc}); run `python -m guardx_amd.build`") from exc
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the ABI drifted
-        fn.restype = res
-        fn.argtypes = args
-    got = lib.gxu_build_id().decode()
-    if got != want:
-        raise ImportError(f"{LIB_PATH} was built from other sources (library {got}, tree {want}); "
-                          "run `python -m guardx_amd.build`")
-    _lib = lib
-    return lib
-
-
-class GxuError(RuntimeError):
-    def __init__(self, status, msg):
-        super().__init__(f"guardx usl status {status}: {msg}")
-        self.status = status
-
-
-def check(status):
-    if status != GXU_OK:
-        msg = load().gxu_last_error()
-        raise GxuError(status, msg.decode() if msg else "")
+_side = _sidelib.Binding("usl", "gxu", SYMBOLS, GXU_OK, "usl")
+LIB_PATH, load, check, GxuError = _side.path, _side.load, _side.check, _side.Error

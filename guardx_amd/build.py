@@ -1,5 +1,5 @@
-"""Build libguardx_hip.so, libguardx_critic.so, libguardx_statewise.so, libguardx_safelayer.so and libguardx_usl.so
-(gfx950) in-tree with hipcc.
+"""Build libguardx_hip.so and the side libraries of LIBRARIES (libguardx_critic.so, libguardx_statewise.so,
+libguardx_safelayer.so, libguardx_usl.so) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -63,30 +63,51 @@ def _extra(src):
 BUILD_ID_FILE = os.path.join(LIB_DIR, "BUILD_ID")
 LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 
-# The batched cost critic (include/guardx_critic.h) is a library of its own with its own build identity, so that it
-# leaves the sources, the flags and the build id of libguardx_hip.so -- and the profiles taken on that build -- alone.
-CRITIC_LIB = os.path.join(LIB_DIR, "libguardx_critic.so")
-CRITIC_SOURCES = ["gx_critic.hip"]
-CRITIC_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_critic.h")]
-CRITIC_BUILD_ID_FILE = os.path.join(LIB_DIR, "CRITIC_BUILD_ID")
+# The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer and the USL policy step.  Each is
+# a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
+# libguardx_hip.so -- and the profiles taken on that build -- alone.
+_SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
 
-# The state-wise (SCPO) policy step (include/guardx_statewise.h): a third library on the same terms.
-STATEWISE_LIB = os.path.join(LIB_DIR, "libguardx_statewise.so")
-STATEWISE_SOURCES = ["gx_statewise.hip"]
-STATEWISE_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_statewise.h")]
-STATEWISE_BUILD_ID_FILE = os.path.join(LIB_DIR, "STATEWISE_BUILD_ID")
 
-# The safety-layer policy step (include/guardx_safelayer.h): a fourth library on the same terms.
-SAFELAYER_LIB = os.path.join(LIB_DIR, "libguardx_safelayer.so")
-SAFELAYER_SOURCES = ["gx_safelayer.hip"]
-SAFELAYER_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_safelayer.h")]
-SAFELAYER_BUILD_ID_FILE = os.path.join(LIB_DIR, "SAFELAYER_BUILD_ID")
+class SideLibrary:
+    """One translation unit, one library: libguardx_<key>.so from <sources> with -D<macro>="<source_hash()>" compiled
+    in (its gx?_build_id()), checked at load time by guardx_amd/_sidelib.py."""
 
-# The USL policy step with its gradient-descent correction (include/guardx_usl.h): a fifth library on the same terms.
-USL_LIB = os.path.join(LIB_DIR, "libguardx_usl.so")
-USL_SOURCES = ["gx_usl.hip"]
-USL_HEADERS = ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_usl.h")]
-USL_BUILD_ID_FILE = os.path.join(LIB_DIR, "USL_BUILD_ID")
+    def __init__(self, key, macro, sources, headers):
+        self.key, self.macro, self.sources = key, macro, sources
+        self.headers = headers + [os.path.join("..", "..", "include", "guardx_%s.h" % key)]
+        self.lib = os.path.join(LIB_DIR, "libguardx_%s.so" % key)
+        self.build_id_file = os.path.join(LIB_DIR, key.upper() + "_BUILD_ID")
+
+    def source_hash(self):
+        """source_hash() of this library: its sources, every project header they include, FLAGS and the compiler"""
+        import hashlib
+        h = hashlib.sha256()
+        h.update(compiler_id().encode() + b"\0")
+        for n in sorted(set(self.sources) | set(self.headers)):
+            h.update(n.encode() + b"\0")
+            with open(os.path.join(CSRC, n), "rb") as f:
+                h.update(f.read())
+        h.update(repr(FLAGS).encode())
+        return h.hexdigest()[:24]
+
+    def built_id(self):
+        try:
+            with open(self.build_id_file) as f:
+                return f.read().strip()
+        except OSError:
+            return None
+
+    def needs_build(self):
+        return not os.path.exists(self.lib) or self.built_id() != self.source_hash()
+
+
+LIBRARIES = {lib.key: lib for lib in (
+    SideLibrary("critic", "GXC_BUILD_ID", ["gx_critic.hip"], _SIDE_HEADERS),
+    SideLibrary("statewise", "GXS_BUILD_ID", ["gx_statewise.hip"], _SIDE_HEADERS),
+    SideLibrary("safelayer", "GXL_BUILD_ID", ["gx_safelayer.hip"], _SIDE_HEADERS),
+    SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _SIDE_HEADERS),
+)}
 
 
 _COMPILER = None
@@ -127,62 +148,6 @@ def source_hash():
     return h.hexdigest()[:24]
 
 
-def critic_source_hash():
-    """source_hash() of libguardx_critic.so: its sources, every project header they include, FLAGS and the compiler
-    (compiled in as gxc_build_id() and checked at load time, guardx_amd/_critic_native.py)."""
-    import hashlib
-    h = hashlib.sha256()
-    h.update(compiler_id().encode() + b"\0")
-    for n in sorted(set(CRITIC_SOURCES) | set(CRITIC_HEADERS)):
-        h.update(n.encode() + b"\0")
-        with open(os.path.join(CSRC, n), "rb") as f:
-            h.update(f.read())
-    h.update(repr(FLAGS).encode())
-    return h.hexdigest()[:24]
-
-
-def statewise_source_hash():
-    """source_hash() of libguardx_statewise.so: its sources, every project header they include, FLAGS and the compiler
-    (compiled in as gxs_build_id() and checked at load time, guardx_amd/_statewise_native.py)."""
-    import hashlib
-    h = hashlib.sha256()
-    h.update(compiler_id().encode() + b"\0")
-    for n in sorted(set(STATEWISE_SOURCES) | set(STATEWISE_HEADERS)):
-        h.update(n.encode() + b"\0")
-        with open(os.path.join(CSRC, n), "rb") as f:
-            h.update(f.read())
-    h.update(repr(FLAGS).encode())
-    return h.hexdigest()[:24]
-
-
-def safelayer_source_hash():
-    """source_hash() of libguardx_safelayer.so: its sources, every project header they include, FLAGS and the compiler
-    (compiled in as gxl_build_id() and checked at load time, guardx_amd/_safelayer_native.py)."""
-    import hashlib
-    h = hashlib.sha256()
-    h.update(compiler_id().encode() + b"\0")
-    for n in sorted(set(SAFELAYER_SOURCES) | set(SAFELAYER_HEADERS)):
-        h.update(n.encode() + b"\0")
-        with open(os.path.join(CSRC, n), "rb") as f:
-            h.update(f.read())
-    h.update(repr(FLAGS).encode())
-    return h.hexdigest()[:24]
-
-
-def usl_source_hash():
-    """source_hash() of libguardx_usl.so: its sources, every project header they include, FLAGS and the compiler
-    (compiled in as gxu_build_id() and checked at load time, guardx_amd/_usl_native.py)."""
-    import hashlib
-    h = hashlib.sha256()
-    h.update(compiler_id().encode() + b"\0")
-    for n in sorted(set(USL_SOURCES) | set(USL_HEADERS)):
-        h.update(n.encode() + b"\0")
-        with open(os.path.join(CSRC, n), "rb") as f:
-            h.update(f.read())
-    h.update(repr(FLAGS).encode())
-    return h.hexdigest()[:24]
-
-
 def _obj(src):
     return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
 
@@ -197,54 +162,6 @@ def built_id():
 
 def needs_build():
     return not os.path.exists(LIB) or built_id() != source_hash()
-
-
-def built_critic_id():
-    try:
-        with open(CRITIC_BUILD_ID_FILE) as f:
-            return f.read().strip()
-    except OSError:
-        return None
-
-
-def critic_needs_build():
-    return not os.path.exists(CRITIC_LIB) or built_critic_id() != critic_source_hash()
-
-
-def built_statewise_id():
-    try:
-        with open(STATEWISE_BUILD_ID_FILE) as f:
-            return f.read().strip()
-    except OSError:
-        return None
-
-
-def statewise_needs_build():
-    return not os.path.exists(STATEWISE_LIB) or built_statewise_id() != statewise_source_hash()
-
-
-def built_safelayer_id():
-    try:
-        with open(SAFELAYER_BUILD_ID_FILE) as f:
-            return f.read().strip()
-    except OSError:
-        return None
-
-
-def safelayer_needs_build():
-    return not os.path.exists(SAFELAYER_LIB) or built_safelayer_id() != safelayer_source_hash()
-
-
-def built_usl_id():
-    try:
-        with open(USL_BUILD_ID_FILE) as f:
-            return f.read().strip()
-    except OSError:
-        return None
-
-
-def usl_needs_build():
-    return not os.path.exists(USL_LIB) or built_usl_id() != usl_source_hash()
 
 
 def _dep_hash(src):
@@ -269,14 +186,9 @@ def build(force=False, verbose=False, jobs=None):
         try:
             if force or needs_build():
                 _build_locked(force, verbose, jobs)
-            if force or critic_needs_build():
-                _build_critic_locked(verbose)
-            if force or statewise_needs_build():
-                _build_statewise_locked(verbose)
-            if force or safelayer_needs_build():
-                _build_safelayer_locked(verbose)
-            if force or usl_needs_build():
-                _build_usl_locked(verbose)
+            for side in LIBRARIES.values():
+                if force or side.needs_build():
+                    _build_side_locked(side, verbose)
             return LIB
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
@@ -320,74 +232,24 @@ def _build_locked(force, verbose, jobs):
     return LIB
 
 
-def _build_critic_locked(verbose):
+def _build_side_locked(side, verbose):
     hipcc = os.environ.get("HIPCC", "hipcc")
-    bid = critic_source_hash()
-    tmp = CRITIC_LIB + ".tmp.%d" % os.getpid()
-    cmd = [hipcc] + FLAGS + ['-DGXC_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
-          [os.path.join(CSRC, s) for s in CRITIC_SOURCES]
+    bid = side.source_hash()
+    tmp = side.lib + ".tmp.%d" % os.getpid()
+    cmd = [hipcc] + FLAGS + ['-D%s="%s"' % (side.macro, bid), "-shared", "-o", tmp] + \
+          [os.path.join(CSRC, s) for s in side.sources]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    os.replace(tmp, CRITIC_LIB)
-    with open(CRITIC_BUILD_ID_FILE + ".tmp", "w") as f:
+    os.replace(tmp, side.lib)
+    with open(side.build_id_file + ".tmp", "w") as f:
         f.write(bid + "\n")
-    os.replace(CRITIC_BUILD_ID_FILE + ".tmp", CRITIC_BUILD_ID_FILE)
-    return CRITIC_LIB
-
-
-def _build_statewise_locked(verbose):
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    bid = statewise_source_hash()
-    tmp = STATEWISE_LIB + ".tmp.%d" % os.getpid()
-    cmd = [hipcc] + FLAGS + ['-DGXS_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
-          [os.path.join(CSRC, s) for s in STATEWISE_SOURCES]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, STATEWISE_LIB)
-    with open(STATEWISE_BUILD_ID_FILE + ".tmp", "w") as f:
-        f.write(bid + "\n")
-    os.replace(STATEWISE_BUILD_ID_FILE + ".tmp", STATEWISE_BUILD_ID_FILE)
-    return STATEWISE_LIB
-
-
-def _build_safelayer_locked(verbose):
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    bid = safelayer_source_hash()
-    tmp = SAFELAYER_LIB + ".tmp.%d" % os.getpid()
-    cmd = [hipcc] + FLAGS + ['-DGXL_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
-          [os.path.join(CSRC, s) for s in SAFELAYER_SOURCES]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, SAFELAYER_LIB)
-    with open(SAFELAYER_BUILD_ID_FILE + ".tmp", "w") as f:
-        f.write(bid + "\n")
-    os.replace(SAFELAYER_BUILD_ID_FILE + ".tmp", SAFELAYER_BUILD_ID_FILE)
-    return SAFELAYER_LIB
-
-
-def _build_usl_locked(verbose):
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    bid = usl_source_hash()
-    tmp = USL_LIB + ".tmp.%d" % os.getpid()
-    cmd = [hipcc] + FLAGS + ['-DGXU_BUILD_ID="%s"' % bid, "-shared", "-o", tmp] + \
-          [os.path.join(CSRC, s) for s in USL_SOURCES]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, USL_LIB)
-    with open(USL_BUILD_ID_FILE + ".tmp", "w") as f:
-        f.write(bid + "\n")
-    os.replace(USL_BUILD_ID_FILE + ".tmp", USL_BUILD_ID_FILE)
-    return USL_LIB
+    os.replace(side.build_id_file + ".tmp", side.build_id_file)
+    return side.lib
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    print("critic build id", built_critic_id())
-    print("statewise build id", built_statewise_id())
-    print("safelayer build id", built_safelayer_id())
-    print("usl build id", built_usl_id())
+    for side in LIBRARIES.values():
+        print(side.key, "build id", side.built_id())

@@ -138,7 +138,7 @@ gxc_status launch(int M, int D, const float* params, const float* x, float* out,
 
 extern "C" const char* gxc_last_error(void) { return g_err.c_str(); }
 
-extern "C" const char* gxc_build_id(void) { return GXC_BUILD_ID; } // guardx_amd/build.py:critic_source_hash()
+extern "C" const char* gxc_build_id(void) { return GXC_BUILD_ID; } // guardx_amd/build.py:LIBRARIES["critic"].source_hash()
 
 extern "C" int64_t gxc_critic_floats(int32_t D, int32_t hidden)
 {

@@ -359,7 +359,7 @@ gxl_status check_shape(const char* who, int D, int A, int H, int HG)
 
 extern "C" const char* gxl_last_error(void) { return g_err.c_str(); }
 
-extern "C" const char* gxl_build_id(void) { return GXL_BUILD_ID; } // guardx_amd/build.py:safelayer_source_hash()
+extern "C" const char* gxl_build_id(void) { return GXL_BUILD_ID; } // guardx_amd/build.py:LIBRARIES["safelayer"].source_hash()
 
 extern "C" int64_t gxl_params_floats(int32_t D, int32_t A, int32_t hidden)
 {

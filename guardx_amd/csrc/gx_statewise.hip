@@ -297,7 +297,7 @@ gxs_status check_shape(const char* who, int Da, int A, int H, int HC)
 
 extern "C" const char* gxs_last_error(void) { return g_err.c_str(); }
 
-extern "C" const char* gxs_build_id(void) { return GXS_BUILD_ID; } // guardx_amd/build.py:statewise_source_hash()
+extern "C" const char* gxs_build_id(void) { return GXS_BUILD_ID; } // guardx_amd/build.py:LIBRARIES["statewise"].source_hash()
 
 extern "C" int64_t gxs_params_floats(int32_t D_aug, int32_t A, int32_t hidden)
 {

@@ -661,7 +661,7 @@ gxu_status raise_lds(const char* who, const void* kernel, size_t lds)
 
 extern "C" const char* gxu_last_error(void) { return g_err.c_str(); }
 
-extern "C" const char* gxu_build_id(void) { return GXU_BUILD_ID; } // guardx_amd/build.py:usl_source_hash()
+extern "C" const char* gxu_build_id(void) { return GXU_BUILD_ID; } // guardx_amd/build.py:LIBRARIES["usl"].source_hash()
 
 extern "C" int64_t gxu_params_floats(int32_t D, int32_t A, int32_t hidden)
 {

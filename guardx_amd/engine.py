@@ -825,7 +825,7 @@ class Engine:
         output='softplus': SCPO's MLPMaxCostCritic (scpo_core.py:158-166), the same layers followed by nn.Softplus
         (beta 1, threshold 20), for rollout_statewise(..., cost_critic=).  The layout is the same; the returned tensor
         carries the declaration (guardx_amd.statewise.critic_output), and each rollout refuses the other kind."""
-        from . import statewise as _sw
+        from . import _closed_loop as _cl, statewise as _sw
         if output not in ('identity', 'softplus'):
             raise ValueError(f"pack_critic: output must be 'identity' or 'softplus', got {output!r}")
         net = getattr(critic, 'v_net', critic)
@@ -837,20 +837,10 @@ class Engine:
             if last.beta != 1 or last.threshold != 20:
                 raise NotImplementedError("pack_critic(output='softplus') supports nn.Softplus(beta=1, threshold=20)")
             mods = mods[:-1]
-        lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
-        if len(lin) != 3:
-            raise NotImplementedError("the cost critic pass supports two hidden layers (--l 2)")
-        if [type(m) for m in mods] != [torch.nn.Linear, torch.nn.Tanh] * 2 + [torch.nn.Linear]:
-            raise NotImplementedError("the cost critic pass supports Tanh hidden activations and a linear output only")
-        if lin[0].out_features != lin[1].out_features or lin[1].in_features != lin[0].out_features \
-                or lin[2].in_features != lin[1].out_features:
-            raise NotImplementedError("the cost critic pass supports two hidden layers of equal width")
-        if lin[0].out_features not in Engine.POLICY_HIDDEN:
-            raise NotImplementedError(f"the cost critic pass supports hidden widths {Engine.POLICY_HIDDEN}")
+        lin = _cl.two_tanh_layers(mods, "the cost critic pass", tanh_tail=" and a linear output only")
         if lin[2].out_features != 1:
             raise NotImplementedError("the cost critic pass supports one output")
-        flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for m in lin for t in (m.weight, m.bias)])
-        flat = flat.to(device) if device is not None else flat
+        flat = _cl.flatten(lin, device)
         setattr(flat, _sw.OUTPUT_ATTR, output)
         return flat
 

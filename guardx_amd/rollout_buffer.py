@@ -145,68 +145,6 @@ def gae_rollout(rew, val, done, last_val=None, gamma=0.99, lam=0.95):
     return adv, ret
 
 
-def cost_rollout_batch(out, gamma=0.99, lam=0.95):
-    """A rollout_policy(..., cost_critic=pack_critic(ac.vc)) result as the batch DeviceCostRolloutBuffer.get() returns
-    after CPO's collection loop (cpo.py:596-660): store() every step, finish_path() with v = vc = 0 for the envs done at
-    that step, a closing finish_path() over every env without bootstrap.  Env-major, flattened:
-    obs act ret adv cost_ret adc logp mu logstd; adv normalised per env, adc centred per env only (cpo.py:142-175)."""
-    for k in ('vc', 'rew', 'val', 'cost', 'done', 'obs'):
-        if k not in out:
-            raise KeyError(f"cost_rollout_batch needs out['{k}'] (rollout_policy(..., cost_critic=...))")
-    T, N = out['rew'].shape
-    adv, ret = gae_rollout(out['rew'], out['val'], out['done'], None, gamma, lam)
-    adc, cost_ret = gae_rollout(out['cost'], out['vc'], out['done'], None, gamma, lam)
-    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
-    adv, adc = env_major(adv), env_major(adc)
-    lib = _native.load()
-    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))
-    _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1, stream))
-    _native.check(lib.gx_adv_normalize(N, T, adc.data_ptr(), 0, stream))
-    A = out['act'].shape[-1]
-    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
-                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
-                cost_ret=env_major(cost_ret).view(N * T), adc=adc.view(N * T),
-                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
-                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous())
-
-
-def statewise_rollout_batch(out, gamma=0.99, lam=0.95, cgamma=1.0, clam=0.95, cost_signal='increment', bootstrap=False):
-    """An Engine.rollout_statewise result as the batch SCPOBufferX.get() returns after SCPO's collection loop
-    (safe_rl_libX/scpo/scpo.py:30-175, 640-720): store() every step, finish_path() with v = vc = 0 for the envs done at
-    that step, a closing finish_path() at the time-out.  The cost channel runs with SCPO's own cgamma / clam
-    (scpo.py:36: no discount of the cost).  Env-major, flattened: obs act ret adv cost_ret adc logp mu logstd; adv
-    normalised per env, adc centred per env only (scpo.py:148-160).
-    cost_signal: 'increment' = out['cost_inc'], the max(cost - M, 0) SCPO defines; 'reference' = out['M']: what
-    scpo.py:647-654 stores as written (its `cost_increase` and `M_next` are the same tensor, which ends up holding M_next).
-    bootstrap: False closes every path at step T - 1 with 0, as SCPO's time-out does (scpo.py:683-686); True bootstraps
-    the envs not done at step T - 1 with val_last / vc_last (a call shorter than the episode)."""
-    if cost_signal not in ('increment', 'reference'):
-        raise ValueError(f"cost_signal must be 'increment' or 'reference', got {cost_signal!r}")
-    for k in ('vc', 'rew', 'val', 'cost_inc', 'M', 'done', 'obs', 'val_last', 'vc_last'):
-        if k not in out:
-            raise KeyError(f"statewise_rollout_batch needs out['{k}'] (Engine.rollout_statewise)")
-    T, N = out['rew'].shape
-    costs = out['cost_inc'] if cost_signal == 'increment' else out['M']
-    lv, lvc = None, None
-    if bootstrap:
-        alive = 1.0 - out['done'][-1]
-        lv, lvc = out['val_last'] * alive, out['vc_last'] * alive
-    adv, ret = gae_rollout(out['rew'], out['val'], out['done'], lv, gamma, lam)
-    adc, cost_ret = gae_rollout(costs, out['vc'], out['done'], lvc, cgamma, clam)
-    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
-    adv, adc = env_major(adv), env_major(adc)
-    lib = _native.load()
-    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))
-    _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1, stream))
-    _native.check(lib.gx_adv_normalize(N, T, adc.data_ptr(), 0, stream))
-    A = out['act'].shape[-1]
-    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
-                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
-                cost_ret=env_major(cost_ret).view(N * T), adc=adc.view(N * T),
-                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
-                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous())
-
-
 def _gae_host(rew, val, done, gamma, lam):
     """gae_rollout + the per-env normalisation for HOST tensors, in plain torch: the same recursion the kernels run
     (paths closed with 0 at every done step and at step T - 1).  Returns (adv normalised, env-major (N, T); ret (T, N))."""
@@ -225,6 +163,80 @@ def _gae_host(rew, val, done, gamma, lam):
     return (adv - mean) / std, ret
 
 
+def _env_major(x):
+    return x.transpose(0, 1).contiguous()   # (T, N, ...) -> (N, T, ...)
+
+
+def _require(out, keys, who, source):
+    for k in keys:
+        if k not in out:
+            raise KeyError(f"{who} needs out['{k}'] ({source})")
+
+
+def _channel(rew, val, done, last_val, gamma, lam, scale=1):
+    """One GAE channel of a rollout, (T, N) tensors -> (advantage: env-major (N, T), per env normalised, or centred only
+    with scale=0; returns-to-go: (T, N)).  Device tensors go through the GAE and normalisation kernels; host tensors (a
+    result moved to the CPU) through the same recursion in torch, which serves the reward channel without bootstrap."""
+    if not rew.is_cuda:
+        if last_val is not None or not scale:
+            raise NotImplementedError("host tensors: only the normalised reward channel without bootstrap")
+        f = lambda x: x.to(torch.float32)   # noqa: E731
+        return _gae_host(f(rew), f(val), f(done), float(gamma), float(lam))
+    T, N = rew.shape
+    adv, ret = gae_rollout(rew, val, done, last_val, gamma, lam)
+    adv = _env_major(adv)
+    _native.check(_native.load().gx_adv_normalize(N, T, adv.data_ptr(), scale,
+                                                  C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))))
+    return adv, ret
+
+
+def _batch(out, adv, ret, **more):
+    """What every *_rollout_batch returns, env-major and flattened: obs act ret adv logp mu logstd from a rollout's `out`
+    and its reward channel, then the path's own time-major tensors `more`."""
+    T, N = out['rew'].shape
+    A = out['act'].shape[-1]
+    flat = lambda x: _env_major(x).view(N * T, *x.shape[2:])   # noqa: E731
+    return dict(obs=flat(out['obs']), act=flat(out['act']), ret=flat(ret), adv=adv.view(N * T),
+                logp=flat(out['logp']), mu=flat(out['mu']),
+                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous(),
+                **{k: flat(v) for k, v in more.items()})
+
+
+def cost_rollout_batch(out, gamma=0.99, lam=0.95):
+    """A rollout_policy(..., cost_critic=pack_critic(ac.vc)) result as the batch DeviceCostRolloutBuffer.get() returns
+    after CPO's collection loop (cpo.py:596-660): store() every step, finish_path() with v = vc = 0 for the envs done at
+    that step, a closing finish_path() over every env without bootstrap.  Env-major, flattened:
+    obs act ret adv cost_ret adc logp mu logstd; adv normalised per env, adc centred per env only (cpo.py:142-175)."""
+    _require(out, ('vc', 'rew', 'val', 'cost', 'done', 'obs'), "cost_rollout_batch", "rollout_policy(..., cost_critic=...)")
+    adv, ret = _channel(out['rew'], out['val'], out['done'], None, gamma, lam)
+    adc, cost_ret = _channel(out['cost'], out['vc'], out['done'], None, gamma, lam, scale=0)
+    return dict(_batch(out, adv, ret, cost_ret=cost_ret), adc=adc.view(-1))
+
+
+def statewise_rollout_batch(out, gamma=0.99, lam=0.95, cgamma=1.0, clam=0.95, cost_signal='increment', bootstrap=False):
+    """An Engine.rollout_statewise result as the batch SCPOBufferX.get() returns after SCPO's collection loop
+    (safe_rl_libX/scpo/scpo.py:30-175, 640-720): store() every step, finish_path() with v = vc = 0 for the envs done at
+    that step, a closing finish_path() at the time-out.  The cost channel runs with SCPO's own cgamma / clam
+    (scpo.py:36: no discount of the cost).  Env-major, flattened: obs act ret adv cost_ret adc logp mu logstd; adv
+    normalised per env, adc centred per env only (scpo.py:148-160).
+    cost_signal: 'increment' = out['cost_inc'], the max(cost - M, 0) SCPO defines; 'reference' = out['M']: what
+    scpo.py:647-654 stores as written (its `cost_increase` and `M_next` are the same tensor, which ends up holding M_next).
+    bootstrap: False closes every path at step T - 1 with 0, as SCPO's time-out does (scpo.py:683-686); True bootstraps
+    the envs not done at step T - 1 with val_last / vc_last (a call shorter than the episode)."""
+    if cost_signal not in ('increment', 'reference'):
+        raise ValueError(f"cost_signal must be 'increment' or 'reference', got {cost_signal!r}")
+    _require(out, ('vc', 'rew', 'val', 'cost_inc', 'M', 'done', 'obs', 'val_last', 'vc_last'),
+             "statewise_rollout_batch", "Engine.rollout_statewise")
+    costs = out['cost_inc'] if cost_signal == 'increment' else out['M']
+    lv, lvc = None, None
+    if bootstrap:
+        alive = 1.0 - out['done'][-1]
+        lv, lvc = out['val_last'] * alive, out['vc_last'] * alive
+    adv, ret = _channel(out['rew'], out['val'], out['done'], lv, gamma, lam)
+    adc, cost_ret = _channel(costs, out['vc'], out['done'], lvc, cgamma, clam, scale=0)
+    return dict(_batch(out, adv, ret, cost_ret=cost_ret), adc=adc.view(-1))
+
+
 def safelayer_rollout_batch(out, gamma=0.99, lam=0.95):
     """An Engine.rollout_safelayer result as the batch SafeLayerBufferX.get() returns after the safelayer learner's
     collection loop (safe_rl_libX/safelayer/safelayer.py:32-154, 514-583): store() every step, finish_path() with v = 0
@@ -232,27 +244,10 @@ def safelayer_rollout_batch(out, gamma=0.99, lam=0.95):
     Env-major, flattened: obs act act_safe ret adv logp mu logstd cost prev_cost; adv normalised per env
     (safelayer.py:137-141).  Device tensors go through the GAE and normalisation kernels; a dict of host tensors (a
     result moved to the CPU) is served by the same recursion in torch."""
-    for k in ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'prev_cost', 'done'):
-        if k not in out:
-            raise KeyError(f"safelayer_rollout_batch needs out['{k}'] (Engine.rollout_safelayer)")
-    T, N = out['rew'].shape
-    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
-    if out['rew'].is_cuda:
-        adv, ret = gae_rollout(out['rew'], out['val'], out['done'], None, gamma, lam)
-        adv = env_major(adv)
-        lib = _native.load()
-        _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1,
-                                           C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))))
-    else:
-        f = lambda x: x.to(torch.float32)   # noqa: E731
-        adv, ret = _gae_host(f(out['rew']), f(out['val']), f(out['done']), float(gamma), float(lam))
-    A = out['act'].shape[-1]
-    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
-                act_safe=env_major(out['act_safe']).view(N * T, -1),
-                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
-                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
-                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous(),
-                cost=env_major(out['cost']).view(N * T), prev_cost=env_major(out['prev_cost']).view(N * T))
+    _require(out, ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'prev_cost', 'done'),
+             "safelayer_rollout_batch", "Engine.rollout_safelayer")
+    adv, ret = _channel(out['rew'], out['val'], out['done'], None, gamma, lam)
+    return _batch(out, adv, ret, act_safe=out['act_safe'], cost=out['cost'], prev_cost=out['prev_cost'])
 
 
 def usl_rollout_batch(out, gamma=0.99, lam=0.95):
@@ -263,28 +258,12 @@ def usl_rollout_batch(out, gamma=0.99, lam=0.95):
     targetc[t] = cost[t] + gamma qc[t + 1] with qc taken as 0 past the end of a path (usl.py:105-107, 125-127): at every
     done step and at step T - 1.  Device tensors go through the GAE and normalisation kernels; a dict of host tensors (a
     result moved to the CPU) is served by the same recursion in torch."""
-    for k in ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'qc', 'done'):
-        if k not in out:
-            raise KeyError(f"usl_rollout_batch needs out['{k}'] (Engine.rollout_usl)")
-    T, N = out['rew'].shape
-    env_major = lambda x: x.transpose(0, 1).contiguous()   # noqa: E731  (T, N, ...) -> (N, T, ...)
+    _require(out, ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'qc', 'done'),
+             "usl_rollout_batch", "Engine.rollout_usl")
+    adv, ret = _channel(out['rew'], out['val'], out['done'], None, gamma, lam)
     f = lambda x: x.to(torch.float32)   # noqa: E731
-    if out['rew'].is_cuda:
-        adv, ret = gae_rollout(out['rew'], out['val'], out['done'], None, gamma, lam)
-        adv = env_major(adv)
-        lib = _native.load()
-        _native.check(lib.gx_adv_normalize(N, T, adv.data_ptr(), 1,
-                                           C.c_void_p(torch._C._cuda_getCurrentRawStream(adv.device.index))))
-    else:
-        adv, ret = _gae_host(f(out['rew']), f(out['val']), f(out['done']), float(gamma), float(lam))
     qc, done = f(out['qc']), f(out['done'])
     q_next = torch.zeros_like(qc)
     q_next[:-1] = qc[1:] * (1.0 - (done[:-1] > 0).to(torch.float32))
     targetc = f(out['cost']) + float(gamma) * q_next
-    A = out['act'].shape[-1]
-    return dict(obs=env_major(out['obs']).view(N * T, -1), act=env_major(out['act']).view(N * T, -1),
-                act_safe=env_major(out['act_safe']).view(N * T, -1),
-                ret=env_major(ret).view(N * T), adv=adv.view(N * T),
-                logp=env_major(out['logp']).view(N * T), mu=env_major(out['mu']).view(N * T, -1),
-                logstd=out['logstd'].reshape(1, A).expand(N * T, A).contiguous(),
-                cost=env_major(out['cost']).view(N * T), targetc=env_major(targetc).view(N * T))
+    return _batch(out, adv, ret, act_safe=out['act_safe'], cost=out['cost'], targetc=targetc)

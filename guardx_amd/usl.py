@@ -19,16 +19,16 @@ import ctypes as C
 
 import torch
 
-from . import _native, _usl_native
+from . import _closed_loop as _cl, _usl_native
+from ._closed_loop import policy_floats  # noqa: F401 (part of this module's surface)
 from .critic import HIDDEN
-from .safelayer import policy_floats
 
 # how pack_q_critic marks what it returns: c_net's input width, checked against D + A at the call
 Q_CRITIC_ATTR = "gx_q_critic"
 
 
 def q_floats(D, A, h):
-    return h * (D + A) + h + h * h + h + h + 1
+    return _cl.net_floats(D + A, 1, h)
 
 
 def pack_q_critic(ccritic, device=None):
@@ -45,26 +45,16 @@ def pack_q_critic(ccritic, device=None):
     if last.beta != 1 or last.threshold != 20:
         raise NotImplementedError("rollout_usl supports nn.Softplus(beta=1, threshold=20)")
     mods = mods[:-1]
-    lin = [m for m in mods if isinstance(m, nn.Linear)]
-    if len(lin) != 3:
-        raise NotImplementedError("rollout_usl supports a c_net with two hidden layers (--l 2)")
-    if [type(m) for m in mods] != [nn.Linear, nn.Tanh] * 2 + [nn.Linear]:
-        raise NotImplementedError("rollout_usl supports a c_net with Tanh hidden activations (activation=nn.Tanh)")
-    if lin[0].out_features != lin[1].out_features or lin[1].in_features != lin[0].out_features \
-            or lin[2].in_features != lin[1].out_features:
-        raise NotImplementedError("rollout_usl supports a c_net with two hidden layers of equal width")
-    if lin[0].out_features not in HIDDEN:
-        raise NotImplementedError(f"rollout_usl supports c_net hidden widths {HIDDEN}")
+    lin = _cl.two_tanh_layers(mods, "rollout_usl", "c_net", " (activation=nn.Tanh)")
     if lin[2].out_features != 1:
         raise NotImplementedError("rollout_usl supports a c_net with one output")
-    flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for m in lin for t in (m.weight, m.bias)])
-    flat = flat.to(device) if device is not None else flat
+    flat = _cl.flatten(lin, device)
     setattr(flat, Q_CRITIC_ATTR, lin[0].in_features)
     return flat
 
 
 def _c_hidden(n, D, A):
-    return next((h for h in HIDDEN if q_floats(D, A, h) == n), None)
+    return _cl.hidden_of(n, lambda h: q_floats(D, A, h))
 
 
 def correction_probe(q_critic, obs, act, delta=0.0, niter=20, eta=0.05, grad_scale=1.0):
@@ -107,39 +97,19 @@ def correction_probe(q_critic, obs, act, delta=0.0, niter=20, eta=0.05, grad_sca
     return out
 
 
-class State:
-    """what the path keeps per engine: the one-set output slab of its env.step launches and its own count of policy
-    steps (the noise counter: 0 at construction, + T per call, not reset by reset())"""
-
-    def __init__(self, env):
-        self.slab = env._out_slab(1)
-        self.steps = 0
+State = _cl.State
 
 
 def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0, niter=20, eta=0.05,
             grad_scale=None):
-    if obs0 is None:
-        obs0 = env._obs
-    if obs0 is None:
-        raise RuntimeError("rollout_usl() before reset()")
-    N, D, A, T = env.env_num, env.obs_flat_size, env.action_space.shape[0], int(T)
-    if T < 1:
-        raise ValueError("rollout_usl: T must be >= 1")
+    obs0, N, D, A, T = _cl.begin(env, "rollout_usl", obs0, T)
     niter = int(niter)
     if niter < 0:
         raise ValueError("rollout_usl: niter must be >= 0")
     if q_critic is None or not torch.is_tensor(q_critic) or getattr(q_critic, Q_CRITIC_ATTR, None) is None:
         raise ValueError("rollout_usl needs q_critic=Engine.pack_q_critic(ac.ccritic, device=...) (the "
                          "declaration travels with the tensor pack_q_critic returns, not with copies of it)")
-    params = params.to(device=env.device, dtype=torch.float32).contiguous()
-    cp = q_critic.to(device=env.device, dtype=torch.float32).contiguous()
-    obs0 = obs0.to(device=env.device, dtype=torch.float32).contiguous()
-    if tuple(obs0.shape) != (N, D):
-        raise ValueError(f"obs0 has shape {tuple(obs0.shape)}; expected {(N, D)}")
-    hidden = next((h for h in HIDDEN if policy_floats(D, A, h) == params.numel()), None)
-    if hidden is None:
-        raise ValueError(f"params has {params.numel()} floats; expected one of "
-                         f"{[policy_floats(D, A, h) for h in HIDDEN]} (hidden {HIDDEN})")
+    params, cp, obs0, hidden = _cl.device_inputs(env, params, q_critic, obs0, D, A)
     c_hidden = _c_hidden(cp.numel(), D, A)
     if c_hidden is None or getattr(q_critic, Q_CRITIC_ATTR) != D + A:
         raise ValueError(f"q_critic has {cp.numel()} floats and reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs; expected "
@@ -153,49 +123,16 @@ def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True
                logp=new(T, N), val=new(T, N), qc=new(T, N), iters=new(T, N), rew=new(T, N), cost=new(T, N),
                done=new(T, N), obs_last=new(N, D), val_last=new(N), logstd=new(A))
     work = new(int(lib.gxu_work_floats(D, A, hidden, c_hidden)))
-    slab = st.slab
-    s_obs, s_rd, s_rew, s_cost, s_done = slab[0][0], slab[1][0], slab[2][0], slab[3][0], slab[4][0]
     a = _usl_native.GxuStepArgs()
-    a.struct_size = C.sizeof(_usl_native.GxuStepArgs)
-    a.N, a.D, a.A, a.hidden, a.c_hidden = N, D, A, hidden, c_hidden
-    a.env_offset = int(env._cfg.env_offset)
-    a.T, a.t = T, 0
+    _cl.fill(a, env, st, out, T, noise_seed, params, work, obs0)
+    a.D, a.hidden, a.c_hidden = D, hidden, c_hidden
     a.correct, a.niter = int(bool(correct)), niter
     a.delta, a.eta = float(delta), float(eta)
     a.grad_scale = 1.0 / N if grad_scale is None else float(grad_scale)
-    a.seed[0], a.seed[1] = int(noise_seed[0]) & 0xFFFFFFFF, int(noise_seed[1]) & 0xFFFFFFFF
-    a.step0 = st.steps & 0xFFFFFFFF
-    a.d_params, a.d_c_params, a.d_work = params.data_ptr(), cp.data_ptr(), work.data_ptr()
-    a.d_obs0, a.d_obs_rd = obs0.data_ptr(), s_rd.data_ptr()
-    a.d_rew_in, a.d_cost_in, a.d_done_in = s_rew.data_ptr(), s_cost.data_ptr(), s_done.data_ptr()
-    for k in ('obs', 'act', 'act_safe', 'mu', 'logp', 'val', 'qc', 'iters', 'rew', 'cost', 'done', 'obs_last',
-              'val_last', 'logstd'):
-        setattr(a, 'd_' + k, out[k].data_ptr())
-    stream = env._raw_stream(env._dev_index)
-    h, ref, spec, spec_ref = env._h, C.byref(a), env._spec, env._spec_ref
-    step_fn, slab_fn, commit_fn, rd_fn = lib.gxu_policy_step, env._gx_step_slab, env._gx_commit, env._lib.gx_reset_done
-    act_ptr, act_stride, slab_ptr = out['act_safe'].data_ptr(), 4 * N * A, slab[6]
-    obs_ptr, rd_ptr = s_obs.data_ptr(), s_rd.data_ptr()
-    env._rd_obs = None
-    with torch.cuda.device(env.device):
-        _usl_native.check(lib.gxu_prepare(D, A, hidden, c_hidden, a.d_params, a.d_c_params, a.d_work, stream))
-        for t in range(T):
-            a.t = t
-            rc = step_fn(ref, stream)
-            if rc:
-                _usl_native.check(rc)
-            # env.step(act_safe[t]) and, in the same launch, what reset_done() returns for it (flags bit 1)
-            rc = slab_fn(h, act_ptr + t * act_stride, slab_ptr, 0, 2, spec_ref, stream)
-            if rc:
-                _native.check(rc)
-            # thread-per-env kernels (env_num > 16384) do not speculate: reset_done as a launch of its own
-            rc = commit_fn(h) if spec.value else rd_fn(h, obs_ptr, rd_ptr, stream)
-            if rc:
-                _native.check(rc)
-        a.t = T
-        _usl_native.check(step_fn(ref, stream))
-    st.steps += T
-    # as rollout_policy leaves them
-    env._obs, env._reward, env._done = out['obs_last'], out['rew'][-1], out['done'][-1]
-    env._info = {'cost': out['cost'][-1]}
+    a.d_c_params = cp.data_ptr()
+
+    def prepare(stream):
+        return lib.gxu_prepare(D, A, hidden, c_hidden, a.d_params, a.d_c_params, a.d_work, stream)
+
+    _cl.run(env, st, a, out, T, prepare, lib.gxu_policy_step, _usl_native.check, out['act_safe'])
     return out

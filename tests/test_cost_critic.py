@@ -155,12 +155,13 @@ def critic_lib():
 
 def test_critic_library_builds_loads_and_binds_its_header(critic_lib):
     from guardx_amd import build, _critic_native
+    libs = build.LIBRARIES
     names = _declared()
     assert len(names) == 5
     for n in names:
         assert hasattr(critic_lib, n), f"{n} declared in guardx_critic.h but not exported"
     assert sorted(_critic_native.SYMBOLS) == names
-    assert critic_lib.gxc_build_id().decode() == build.critic_source_hash() == build.built_critic_id()
+    assert critic_lib.gxc_build_id().decode() == libs["critic"].source_hash() == libs["critic"].built_id()
     assert os.path.basename(_critic_native.LIB_PATH) == "libguardx_critic.so"
     # its own library: none of its symbols in libguardx_hip.so, and the main library's identity is untouched
     from guardx_amd import _native

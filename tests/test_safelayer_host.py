@@ -92,25 +92,27 @@ def test_correction32_against_correction64():
 # ---------------------------------------------------------------------------------------------------------------------
 def test_safelayer_source_hash_covers_its_sources():
     from guardx_amd import build
-    assert build.SAFELAYER_SOURCES == ["gx_safelayer.hip"]
+    libs = build.LIBRARIES
+    assert libs["safelayer"].sources == ["gx_safelayer.hip"]
     incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_safelayer.hip")).read())
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in build.SAFELAYER_HEADERS}
+    have = {norm(h) for h in libs["safelayer"].headers}
     assert {norm(i) for i in incs} <= have
     assert norm("gx_device.h") in have                                # gx_policy.h's own include
     # its own library: nothing of it is hashed into the three older ones, whose identities stand
-    older = set(build.SOURCES) | set(build.CRITIC_SOURCES) | set(build.STATEWISE_SOURCES)
-    assert not (set(build.SAFELAYER_SOURCES) & older)
-    assert all("safelayer" not in h for h in build.HEADERS + build.CRITIC_HEADERS + build.STATEWISE_HEADERS)
+    older = set(build.SOURCES) | set(libs["critic"].sources) | set(libs["statewise"].sources)
+    assert not (set(libs["safelayer"].sources) & older)
+    assert all("safelayer" not in h for h in build.HEADERS + libs["critic"].headers + libs["statewise"].headers)
     recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
     assert build.source_hash() == recorded
-    ids = {build.safelayer_source_hash(), build.statewise_source_hash(), build.critic_source_hash(), build.source_hash()}
-    assert len(ids) == 4 and len(build.safelayer_source_hash()) == 24
+    ids = {libs["safelayer"].source_hash(), libs["statewise"].source_hash(), libs["critic"].source_hash(), build.source_hash()}
+    assert len(ids) == 4 and len(libs["safelayer"].source_hash()) == 24
 
 
 def test_safelayer_hash_changes_with_a_source(monkeypatch, tmp_path):
     from guardx_amd import build
-    before = build.safelayer_source_hash()
+    libs = build.LIBRARIES
+    before = libs["safelayer"].source_hash()
     for n in ["gx_safelayer.hip", "gx_device.h", "gx_policy.h"]:
         (tmp_path / n).write_bytes(open(os.path.join(build.CSRC, n), "rb").read())
     inc = tmp_path.parent / "include_sl"
@@ -118,8 +120,8 @@ def test_safelayer_hash_changes_with_a_source(monkeypatch, tmp_path):
     hdr = open(os.path.join(ROOT, "include", "guardx_safelayer.h"), "rb").read()
     (inc / "guardx_safelayer.h").write_bytes(hdr + b"\n")
     monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    monkeypatch.setattr(build, "SAFELAYER_HEADERS", ["gx_device.h", "gx_policy.h", os.path.join("..", "include_sl", "guardx_safelayer.h")])
-    assert build.safelayer_source_hash() != before                    # the header is part of the identity
+    monkeypatch.setattr(libs["safelayer"], "headers", ["gx_device.h", "gx_policy.h", os.path.join("..", "include_sl", "guardx_safelayer.h")])
+    assert libs["safelayer"].source_hash() != before                    # the header is part of the identity
 
 
 def _header():
@@ -186,10 +188,11 @@ def sl_lib():
 def test_export_list_and_build_id_round_trip(sl_lib):
     import subprocess
     from guardx_amd import build, _safelayer_native as n, _native, _critic_native, _statewise_native
+    libs = build.LIBRARIES
     out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxl_", ln))
     assert exported == sorted(_prototypes())
-    assert sl_lib.gxl_build_id().decode() == build.safelayer_source_hash() == build.built_safelayer_id()
+    assert sl_lib.gxl_build_id().decode() == libs["safelayer"].source_hash() == libs["safelayer"].built_id()
     for other in (_native.LIB_PATH, _critic_native.LIB_PATH, _statewise_native.LIB_PATH):
         lib = C.CDLL(other)
         assert not any(hasattr(lib, s) for s in n.SYMBOLS)
@@ -197,9 +200,10 @@ def test_export_list_and_build_id_round_trip(sl_lib):
 
 def test_a_foreign_build_id_is_refused(sl_lib, monkeypatch):
     from guardx_amd import build, _safelayer_native as n
-    monkeypatch.setattr(n, "_lib", None)
-    monkeypatch.setattr(build, "safelayer_source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(build, "safelayer_needs_build", lambda: False)
+    libs = build.LIBRARIES
+    monkeypatch.setattr(n._side, "_lib", None)
+    monkeypatch.setattr(libs["safelayer"], "source_hash", lambda: "0" * 24)
+    monkeypatch.setattr(libs["safelayer"], "needs_build", lambda: False)
     with pytest.raises(ImportError, match="built from other sources"):
         n.load()
 

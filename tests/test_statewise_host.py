@@ -66,24 +66,26 @@ def test_scpo_actor_critic_packs_on_the_augmented_width():
 # ---------------------------------------------------------------------------------------------------------------------
 def test_statewise_source_hash_covers_its_sources():
     from guardx_amd import build
-    assert build.STATEWISE_SOURCES == ["gx_statewise.hip"]
+    libs = build.LIBRARIES
+    assert libs["statewise"].sources == ["gx_statewise.hip"]
     incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_statewise.hip")).read())
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in build.STATEWISE_HEADERS}
+    have = {norm(h) for h in libs["statewise"].headers}
     assert {norm(i) for i in incs} <= have
     assert norm("gx_device.h") in have                                # gx_policy.h's own include
     # its own library: nothing of it is hashed into the main library or the critic's, whose identities stand
-    assert not (set(build.STATEWISE_SOURCES) & (set(build.SOURCES) | set(build.CRITIC_SOURCES)))
-    assert all("statewise" not in h for h in build.HEADERS + build.CRITIC_HEADERS)
+    assert not (set(libs["statewise"].sources) & (set(build.SOURCES) | set(libs["critic"].sources)))
+    assert all("statewise" not in h for h in build.HEADERS + libs["critic"].headers)
     recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
     assert build.source_hash() == recorded
-    assert len(build.statewise_source_hash()) == 24
-    assert len({build.statewise_source_hash(), build.critic_source_hash(), build.source_hash()}) == 3
+    assert len(libs["statewise"].source_hash()) == 24
+    assert len({libs["statewise"].source_hash(), libs["critic"].source_hash(), build.source_hash()}) == 3
 
 
 def test_statewise_hash_changes_with_a_source(monkeypatch, tmp_path):
     from guardx_amd import build
-    before = build.statewise_source_hash()
+    libs = build.LIBRARIES
+    before = libs["statewise"].source_hash()
     for n in ["gx_statewise.hip", "gx_device.h", "gx_policy.h"]:
         (tmp_path / n).write_bytes(open(os.path.join(build.CSRC, n), "rb").read())
     inc = tmp_path.parent / "include_sw"
@@ -91,8 +93,8 @@ def test_statewise_hash_changes_with_a_source(monkeypatch, tmp_path):
     hdr = open(os.path.join(ROOT, "include", "guardx_statewise.h"), "rb").read()
     (inc / "guardx_statewise.h").write_bytes(hdr + b"\n")
     monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    monkeypatch.setattr(build, "STATEWISE_HEADERS", ["gx_device.h", "gx_policy.h", os.path.join("..", "include_sw", "guardx_statewise.h")])
-    assert build.statewise_source_hash() != before                    # the header is part of the identity
+    monkeypatch.setattr(libs["statewise"], "headers", ["gx_device.h", "gx_policy.h", os.path.join("..", "include_sw", "guardx_statewise.h")])
+    assert libs["statewise"].source_hash() != before                    # the header is part of the identity
 
 
 def _header():
@@ -159,10 +161,11 @@ def sw_lib():
 def test_export_list_equals_the_header(sw_lib):
     import subprocess
     from guardx_amd import build, _statewise_native as n, _native, _critic_native
+    libs = build.LIBRARIES
     out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxs_", ln))
     assert exported == sorted(_prototypes())
-    assert sw_lib.gxs_build_id().decode() == build.statewise_source_hash() == build.built_statewise_id()
+    assert sw_lib.gxs_build_id().decode() == libs["statewise"].source_hash() == libs["statewise"].built_id()
     for other in (_native.LIB_PATH, _critic_native.LIB_PATH):
         lib = C.CDLL(other)
         assert not any(hasattr(lib, s) for s in n.SYMBOLS)

@@ -56,19 +56,20 @@ def test_pack_q_critic():
 # ---------------------------------------------------------------------------------------------------------------------
 def test_usl_source_hash_covers_its_sources_and_leaves_the_older_libraries_alone():
     from guardx_amd import build
-    assert build.USL_SOURCES == ["gx_usl.hip"]
+    libs = build.LIBRARIES
+    assert libs["usl"].sources == ["gx_usl.hip"]
     incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_usl.hip")).read())
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in build.USL_HEADERS}
+    have = {norm(h) for h in libs["usl"].headers}
     assert {norm(i) for i in incs} <= have and norm("gx_device.h") in have
-    older = set(build.SOURCES) | set(build.CRITIC_SOURCES) | set(build.STATEWISE_SOURCES) | set(build.SAFELAYER_SOURCES)
-    assert not (set(build.USL_SOURCES) & older)
-    assert all("usl" not in h for h in build.HEADERS + build.CRITIC_HEADERS + build.STATEWISE_HEADERS + build.SAFELAYER_HEADERS)
+    older = set(build.SOURCES) | set(libs["critic"].sources) | set(libs["statewise"].sources) | set(libs["safelayer"].sources)
+    assert not (set(libs["usl"].sources) & older)
+    assert all("usl" not in h for h in build.HEADERS + libs["critic"].headers + libs["statewise"].headers + libs["safelayer"].headers)
     recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
     assert build.source_hash() == recorded
-    ids = {build.usl_source_hash(), build.safelayer_source_hash(), build.statewise_source_hash(),
-           build.critic_source_hash(), build.source_hash()}
-    assert len(ids) == 5 and len(build.usl_source_hash()) == 24
+    ids = {libs["usl"].source_hash(), libs["safelayer"].source_hash(), libs["statewise"].source_hash(),
+           libs["critic"].source_hash(), build.source_hash()}
+    assert len(ids) == 5 and len(libs["usl"].source_hash()) == 24
 
 
 def _header():
@@ -134,10 +135,11 @@ def usl_lib():
 def test_export_list_and_build_id_round_trip(usl_lib):
     import subprocess
     from guardx_amd import build, _usl_native as n, _native, _critic_native, _statewise_native, _safelayer_native
+    libs = build.LIBRARIES
     out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxu_", ln))
     assert exported == sorted(_prototypes())
-    assert usl_lib.gxu_build_id().decode() == build.usl_source_hash() == build.built_usl_id()
+    assert usl_lib.gxu_build_id().decode() == libs["usl"].source_hash() == libs["usl"].built_id()
     for other in (_native.LIB_PATH, _critic_native.LIB_PATH, _statewise_native.LIB_PATH, _safelayer_native.LIB_PATH):
         lib = C.CDLL(other)
         assert not any(hasattr(lib, s) for s in n.SYMBOLS)
@@ -145,9 +147,10 @@ def test_export_list_and_build_id_round_trip(usl_lib):
 
 def test_a_foreign_build_id_is_refused(usl_lib, monkeypatch):
     from guardx_amd import build, _usl_native as n
-    monkeypatch.setattr(n, "_lib", None)
-    monkeypatch.setattr(build, "usl_source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(build, "usl_needs_build", lambda: False)
+    libs = build.LIBRARIES
+    monkeypatch.setattr(n._side, "_lib", None)
+    monkeypatch.setattr(libs["usl"], "source_hash", lambda: "0" * 24)
+    monkeypatch.setattr(libs["usl"], "needs_build", lambda: False)
     with pytest.raises(ImportError, match="built from other sources"):
         n.load()
 
