@@ -26,6 +26,16 @@ def hidden_of(n, floats):
     return next((h for h in HIDDEN if floats(h) == n), None)
 
 
+def q_floats(D, A, h):
+    """pack_q_critic: c_net of the USL and the LPG learners, one output on D + A inputs"""
+    return net_floats(D + A, 1, h)
+
+
+def q_hidden(n, D, A):
+    """c_net's hidden width, read off the size of the packed tensor, or None"""
+    return hidden_of(n, lambda h: q_floats(D, A, h))
+
+
 def two_tanh_layers(mods, who, net="", tanh_tail=""):
     """The three Linear modules of `mods` = Linear/Tanh/Linear/Tanh/Linear with hidden layers of one width of HIDDEN;
     anything else raises NotImplementedError in the words of `who` (and of its network `net`, when it names one)."""

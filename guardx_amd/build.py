@@ -1,5 +1,5 @@
 """Build libguardx_hip.so and the side libraries of LIBRARIES (libguardx_critic.so, libguardx_statewise.so,
-libguardx_safelayer.so, libguardx_usl.so) for gfx950 in-tree with hipcc.
+libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -63,10 +63,13 @@ def _extra(src):
 BUILD_ID_FILE = os.path.join(LIB_DIR, "BUILD_ID")
 LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 
-# The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer and the USL policy step.  Each is
-# a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
+# The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer, the USL and the LPG policy step.
+# Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
 # libguardx_hip.so -- and the profiles taken on that build -- alone.
 _SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
+# c_net's device code, shared by the two learners that correct the action with a Q critic (and by them alone: the
+# older libraries' build ids do not cover it)
+_Q_HEADERS = _SIDE_HEADERS + ["gx_qcritic.h"]
 
 
 class SideLibrary:
@@ -106,7 +109,8 @@ LIBRARIES = {lib.key: lib for lib in (
     SideLibrary("critic", "GXC_BUILD_ID", ["gx_critic.hip"], _SIDE_HEADERS),
     SideLibrary("statewise", "GXS_BUILD_ID", ["gx_statewise.hip"], _SIDE_HEADERS),
     SideLibrary("safelayer", "GXL_BUILD_ID", ["gx_safelayer.hip"], _SIDE_HEADERS),
-    SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _SIDE_HEADERS),
+    SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _Q_HEADERS),
+    SideLibrary("lpg", "GXP_BUILD_ID", ["gx_lpg.hip"], _Q_HEADERS),
 )}
 
 
@@ -177,7 +181,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All five libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All six libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)

@@ -335,6 +335,7 @@ class Engine:
         self._statewise = None       # rollout_statewise's M / first / step counter (guardx_amd/statewise.py), made on first use
         self._safelayer = None       # rollout_safelayer's prev_c / step counter (guardx_amd/safelayer.py), made on first use
         self._usl = None             # rollout_usl's step counter and slab (guardx_amd/usl.py), made on first use
+        self._lpg = None             # rollout_lpg's q_init / step counter and slab (guardx_amd/lpg.py), made on first use
         self._obs = None
         self._reward = None
         self._done = None
@@ -912,6 +913,30 @@ class Engine:
         advance it."""
         from . import usl as _usl
         return _usl.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, niter, eta, grad_scale)
+
+    def rollout_lpg(self, params, T, obs0=None, noise_seed=(0, 0), *, q_critic, correct=True, delta=0.0, store_init=True,
+                    grad_scale=None, step_sign=1.0):
+        """T x (ac.step -> gradient projection -> env.step(act_safe) -> reset_done) on device: the LPG learner's
+        collection loop (lpg.py:486-564, lpg_core.py:161-198).  `params` = pack_actor_critic(ac), `q_critic` =
+        pack_q_critic(ac.ccritic) (LPG's C_Critic.c_net is USL's module).  qc = Q(obs, act) on the sampled action.
+        store_init=True (the call that starts an epoch) keeps q_init = qc[0] per env, as C_Critic.store_init does;
+        store_init=False uses the values of an earlier call.  With correct=True, rows with qc > delta get
+        a + step_sign lam G, G = grad_scale dQ(obs, 0)/da (the gradient at the ZERO action) and
+        lam = max((G . a - |delta - q_init|) / (G . G), 0): no clamp, no iteration, no epsilon in the denominator
+        (include/guardx_lpg.h fixes the order of operations and lists the reference's quirks).  grad_scale=None is
+        1 / env_num, the reference's pred_0.mean().backward() -- here the factor does NOT cancel; 1.0 is the unscaled
+        form.  step_sign=+1.0 is the reference as written (up the gradient), -1.0 the other sign.  A zero gradient gives
+        lam = 0 when |delta - q_init| > 0 and a NaN action at 0 / 0, which the env's NaN guard handles.
+        correct=False is the learner's warm-up branch: act_safe = act; qc and q_init are still produced.
+        Two launches per control step (guardx_amd/lpg.py).
+        Returns a dict of time-major tensors: obs (T,N,D), act [the actor's sample; logp is its log-probability],
+        act_safe [what env.step received], mu (T,N,A), logp, val, qc, rew, cost, done (T,N), lam (T,N) [the multiplier
+        applied, 0 for an uncorrected row], plus obs_last (N,D), val_last (N,), logstd (A,) and q_init (N,) [a copy of
+        the values the call used].  q_init (zero at construction) persists across calls and is not cleared by reset() or
+        a done env.  The noise counter is this path's own (0 at construction, + T per call, not reset by reset());
+        step(), reset() and the other rollouts neither read nor change either."""
+        from . import lpg as _lpg
+        return _lpg.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, store_init, grad_scale, step_sign)
 
     def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of

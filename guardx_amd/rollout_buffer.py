@@ -250,6 +250,19 @@ def safelayer_rollout_batch(out, gamma=0.99, lam=0.95):
     return _batch(out, adv, ret, act_safe=out['act_safe'], cost=out['cost'], prev_cost=out['prev_cost'])
 
 
+def _q_target_batch(out, gamma, lam, who, source):
+    """USLBufferX.get() and LPGBufferX.get(): the two classes keep the same fields, close paths the same way and build
+    the same targetc (usl.py:26-159 and lpg.py:26-159 differ in their names only)"""
+    _require(out, ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'qc', 'done'), who, source)
+    adv, ret = _channel(out['rew'], out['val'], out['done'], None, gamma, lam)
+    f = lambda x: x.to(torch.float32)   # noqa: E731
+    qc, done = f(out['qc']), f(out['done'])
+    q_next = torch.zeros_like(qc)
+    q_next[:-1] = qc[1:] * (1.0 - (done[:-1] > 0).to(torch.float32))
+    targetc = f(out['cost']) + float(gamma) * q_next
+    return _batch(out, adv, ret, act_safe=out['act_safe'], cost=out['cost'], targetc=targetc)
+
+
 def usl_rollout_batch(out, gamma=0.99, lam=0.95):
     """An Engine.rollout_usl result as the batch USLBufferX.get() returns after the USL learner's collection loop
     (safe_rl_libX/usl/usl.py:50-159, 478-553): store() every step, finish_path() with v = 0 for the envs done at that
@@ -258,12 +271,13 @@ def usl_rollout_batch(out, gamma=0.99, lam=0.95):
     targetc[t] = cost[t] + gamma qc[t + 1] with qc taken as 0 past the end of a path (usl.py:105-107, 125-127): at every
     done step and at step T - 1.  Device tensors go through the GAE and normalisation kernels; a dict of host tensors (a
     result moved to the CPU) is served by the same recursion in torch."""
-    _require(out, ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'qc', 'done'),
-             "usl_rollout_batch", "Engine.rollout_usl")
-    adv, ret = _channel(out['rew'], out['val'], out['done'], None, gamma, lam)
-    f = lambda x: x.to(torch.float32)   # noqa: E731
-    qc, done = f(out['qc']), f(out['done'])
-    q_next = torch.zeros_like(qc)
-    q_next[:-1] = qc[1:] * (1.0 - (done[:-1] > 0).to(torch.float32))
-    targetc = f(out['cost']) + float(gamma) * q_next
-    return _batch(out, adv, ret, act_safe=out['act_safe'], cost=out['cost'], targetc=targetc)
+    return _q_target_batch(out, gamma, lam, "usl_rollout_batch", "Engine.rollout_usl")
+
+
+def lpg_rollout_batch(out, gamma=0.99, lam=0.95):
+    """An Engine.rollout_lpg result as the batch LPGBufferX.get() returns after the LPG learner's collection loop
+    (safe_rl_libX/lpg/lpg.py:50-159, 486-564): the same buffer as USL's under another name, so the same batch as
+    usl_rollout_batch: obs act act_safe ret adv logp mu logstd cost targetc, env-major and flattened, adv normalised per
+    env, targetc[t] = cost[t] + gamma qc[t + 1] with qc of the UNCORRECTED action and 0 past the end of a path.  (`lam`
+    here is GAE's lambda; out['lam'], the projection's multiplier, is not part of the batch.)"""
+    return _q_target_batch(out, gamma, lam, "lpg_rollout_batch", "Engine.rollout_lpg")

@@ -20,15 +20,11 @@ import ctypes as C
 import torch
 
 from . import _closed_loop as _cl, _usl_native
-from ._closed_loop import policy_floats  # noqa: F401 (part of this module's surface)
+from ._closed_loop import policy_floats, q_floats  # noqa: F401 (part of this module's surface)
 from .critic import HIDDEN
 
 # how pack_q_critic marks what it returns: c_net's input width, checked against D + A at the call
 Q_CRITIC_ATTR = "gx_q_critic"
-
-
-def q_floats(D, A, h):
-    return _cl.net_floats(D + A, 1, h)
 
 
 def pack_q_critic(ccritic, device=None):
@@ -53,10 +49,6 @@ def pack_q_critic(ccritic, device=None):
     return flat
 
 
-def _c_hidden(n, D, A):
-    return _cl.hidden_of(n, lambda h: q_floats(D, A, h))
-
-
 def correction_probe(q_critic, obs, act, delta=0.0, niter=20, eta=0.05, grad_scale=1.0):
     """the iteration alone as the kernel evaluates it (gxu_correction_probe): q_critic from pack_q_critic, obs (n, D)
     and act (n, A) float32 device tensors -> dict a_safe (n, A), q0 (n,), grad0 (n, A) [the scaled gradient of the first
@@ -75,7 +67,7 @@ def correction_probe(q_critic, obs, act, delta=0.0, niter=20, eta=0.05, grad_sca
         raise ValueError("correction_probe: more than 2^31 - 1 rows")
     if getattr(q_critic, Q_CRITIC_ATTR, D + A) != D + A:
         raise ValueError(f"correction_probe: q_critic reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs, obs and act have {D} + {A}")
-    hc = _c_hidden(q_critic.numel(), D, A)
+    hc = _cl.q_hidden(q_critic.numel(), D, A)
     if hc is None:
         raise ValueError(f"q_critic has {q_critic.numel()} floats; expected one of {[q_floats(D, A, h) for h in HIDDEN]} "
                          f"(hidden {HIDDEN}) for {D} + {A} inputs")
@@ -110,7 +102,7 @@ def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True
         raise ValueError("rollout_usl needs q_critic=Engine.pack_q_critic(ac.ccritic, device=...) (the "
                          "declaration travels with the tensor pack_q_critic returns, not with copies of it)")
     params, cp, obs0, hidden = _cl.device_inputs(env, params, q_critic, obs0, D, A)
-    c_hidden = _c_hidden(cp.numel(), D, A)
+    c_hidden = _cl.q_hidden(cp.numel(), D, A)
     if c_hidden is None or getattr(q_critic, Q_CRITIC_ATTR) != D + A:
         raise ValueError(f"q_critic has {cp.numel()} floats and reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs; expected "
                          f"one of {[q_floats(D, A, h) for h in HIDDEN]} (hidden {HIDDEN}) for {D} + {A} inputs")
