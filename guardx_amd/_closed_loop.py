@@ -1,5 +1,6 @@
-"""What the closed-loop rollouts with a third network share (statewise.py, safelayer.py, usl.py): the sizes of the packed
-networks, the checks of the inputs, the common fields of a gx?_step_args, the loop itself -- per control step the
+"""What the closed-loop rollouts with a third network share (statewise.py, safelayer.py, usl.py, lpg.py): the sizes of
+the packed networks, the checks of the inputs (for the two learners with a Q critic, usl.py and lpg.py, also those of
+their probes and the tensors their rollouts return), the common fields of a gx?_step_args, the loop itself -- per control step the
 path's policy-step launch and one `gx_step_slab` launch (env.step with the speculated reset_done, committed on the
 host) -- and what the loop leaves on the engine, which is what rollout_policy leaves.
 """
@@ -34,6 +35,69 @@ def q_floats(D, A, h):
 def q_hidden(n, D, A):
     """c_net's hidden width, read off the size of the packed tensor, or None"""
     return hidden_of(n, lambda h: q_floats(D, A, h))
+
+
+# how pack_q_critic marks what it returns: c_net's input width, checked against D + A at the call
+Q_CRITIC_ATTR = "gx_q_critic"
+
+
+def _listed(parts):
+    return ", ".join(parts[:-1]) + " and " + parts[-1]
+
+
+def q_probe_inputs(name, q_critic, obs, act, extra=()):
+    """The checks of a Q critic's probe `name` on q_critic, obs (n, D), act (n, A) and the per-row tensors `extra`
+    ((argument name, tensor (n,)), ...) -> q_critic, obs, act contiguous, n, D, A and c_net's hidden width"""
+    names = ["q_critic", "obs", "act"] + [k for k, _ in extra]
+    for t in [q_critic, obs, act] + [v for _, v in extra]:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise ValueError(f"{name}: {_listed(names)} must be float32 device tensors")
+    if obs.dim() != 2 or act.dim() != 2 or obs.shape[0] != act.shape[0] \
+            or any(tuple(v.shape) != (obs.shape[0],) for _, v in extra):
+        raise ValueError(f"{name}: " + _listed(["obs must be (n, D)", "act (n, A)"] + [k + " (n,)" for k, _ in extra]))
+    n, D = obs.shape
+    A = act.shape[1]
+    if n >= 2 ** 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 rows")
+    if getattr(q_critic, Q_CRITIC_ATTR, D + A) != D + A:
+        raise ValueError(f"{name}: q_critic reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs, obs and act have {D} + {A}")
+    hc = q_hidden(q_critic.numel(), D, A)
+    if hc is None:
+        raise ValueError(f"q_critic has {q_critic.numel()} floats; expected one of {[q_floats(D, A, h) for h in HIDDEN]} "
+                         f"(hidden {HIDDEN}) for {D} + {A} inputs")
+    return q_critic.contiguous(), obs.contiguous(), act.contiguous(), n, D, A, hc
+
+
+def q_probe_work(name, floats, A, device):
+    """the probe's scratch of `floats` = gx?_probe_work_floats(...) floats"""
+    if floats < 0:
+        raise NotImplementedError(f"{name} supports an even action width <= 16, not {A}")
+    return torch.empty(floats, dtype=torch.float32, device=device)
+
+
+def q_rollout_inputs(env, name, params, q_critic, obs0, T):
+    """The checks of a rollout `name` with a Q critic -> params, q_critic and obs0 on the engine's device, N, D, A, T, the
+    policy's hidden width and c_net's"""
+    obs0, N, D, A, T = begin(env, name, obs0, T)
+    if q_critic is None or not torch.is_tensor(q_critic) or getattr(q_critic, Q_CRITIC_ATTR, None) is None:
+        raise ValueError(f"{name} needs q_critic=Engine.pack_q_critic(ac.ccritic, device=...) (the "
+                         "declaration travels with the tensor pack_q_critic returns, not with copies of it)")
+    params, cp, obs0, hidden = device_inputs(env, params, q_critic, obs0, D, A)
+    c_hidden = q_hidden(cp.numel(), D, A)
+    if c_hidden is None or getattr(q_critic, Q_CRITIC_ATTR) != D + A:
+        raise ValueError(f"q_critic has {cp.numel()} floats and reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs; expected "
+                         f"one of {[q_floats(D, A, h) for h in HIDDEN]} (hidden {HIDDEN}) for {D} + {A} inputs")
+    return params, cp, obs0, N, D, A, T, hidden, c_hidden
+
+
+def q_rollout_out(env, T, N, D, A, own):
+    """what both rollouts with a Q critic return, and the path's own (T, N) tensor `own`"""
+    new = env._new
+    out = dict(obs=new(T, N, D), act=new(T, N, A), act_safe=new(T, N, A), mu=new(T, N, A), logp=new(T, N), val=new(T, N),
+               qc=new(T, N), rew=new(T, N), cost=new(T, N), done=new(T, N), obs_last=new(N, D), val_last=new(N),
+               logstd=new(A))
+    out[own] = new(T, N)
+    return out
 
 
 def two_tanh_layers(mods, who, net="", tanh_tail=""):

@@ -67,9 +67,9 @@ LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 # Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
 # libguardx_hip.so -- and the profiles taken on that build -- alone.
 _SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
-# c_net's device code, shared by the two learners that correct the action with a Q critic (and by them alone: the
-# older libraries' build ids do not cover it)
-_Q_HEADERS = _SIDE_HEADERS + ["gx_qcritic.h"]
+# c_net's device code and the step libraries' shared front end and host side, shared by the two learners that correct the
+# action with a Q critic (and by them alone: the older libraries' build ids do not cover them)
+_Q_HEADERS = _SIDE_HEADERS + ["gx_qcritic.h", "gx_qstep.h"]
 
 
 class SideLibrary:

@@ -1,8 +1,10 @@
 // gx_qcritic.h -- the cost critic Q(obs, act) = Softplus(c_net(cat(obs, act))) of the USL and the LPG learners as device
-// code: what gx_usl.hip and gx_lpg.hip share.  The 16-env / 768-thread workgroup's constants, c_net's part of the LDS and
-// its staging, Softplus and its derivative, the MFMA chains of the hidden layers (forward, and backward against
-// (1 - h2^2) w3), the 16-lane output sums and the kernel that transposes the hidden layers into a path's workspace.  The
-// operation order of every function here is the one include/guardx_usl.h fixes; include/guardx_lpg.h refers to it.
+// code, for gx_usl.hip and gx_lpg.hip (through gx_qstep.h, which holds what their step and probe kernels and their host
+// sides share).  The 16-env / 768-thread workgroup's constants, c_net's part of the LDS and its staging, Softplus and its
+// derivative, the MFMA chains of the hidden layers (forward, and backward against (1 - h2^2) w3), the 16-lane output
+// sums, q_pass -- one forward pass over c_net, with or without the action terms and the backward pass: every trip of
+// USL's iteration and both of LPG's passes -- and the kernel that transposes the hidden layers into a path's workspace.
+// The operation order of every function here is the one include/guardx_usl.h fixes; include/guardx_lpg.h refers to it.
 // One translation unit per library: everything sits in an unnamed namespace.
 #ifndef GX_QCRITIC_H
 #define GX_QCRITIC_H
@@ -22,8 +24,9 @@ GX_HD int64_t net_floats(int D, int Out, int H) { return (int64_t)H * D + H + (i
 
 GX_HD int64_t wt_floats(int D, int H) { return (int64_t)pad4(D) * H + (int64_t)H * H; }
 
-// waves that share c_net's unit tiles in the iteration, and tiles per wave
+// waves that share c_net's unit tiles in a pass, and tiles per wave
 GX_HD int q_waves(int HC) { return HC == 256 ? 8 : HC / 16; }
+constexpr int q_tiles(int HC) { return HC == 256 ? 2 : 1; }
 
 // LDS of the Q part, in floats: b1 b2 w3 b3 | W1 action block [A][HC] | P [16][HC + 4] | a [16][17] | s~ [16][17] |
 // z3 [16] | live [16] | (HC == 64: Wt2 [64][64] | W2 [64][64])
@@ -220,6 +223,117 @@ GX_D void q_stage(float* lds, const QLds& L, const QArgs& q, int tid)
             lds[L.Wt2 + (i & 63) * 64 + (i >> 6)] = w;
         }
     for (int i = tid; i < kEnv * kAS; i += kThreads) lds[L.act + i] = 0.0f; // (columns A .. stay zero: the padded k-steps)
+}
+
+// this lane's B operands of the action k-steps of its wave's tiles, W1[unit][D + 4 s + kq]: loaded once, used by every
+// pass that takes the action terms
+template <int HC>
+GX_D void q_load_wa(float (&wa)[kMaxA / 4][q_tiles(HC)], const QArgs& q, int tid)
+{
+    constexpr int TT = q_tiles(HC);
+    const int wave = tid >> 6, lw = tid & 63, c16 = lw & 15, kq = lw >> 4;
+    const int in = q.D + q.A, col0 = 16 * TT * wave;
+    if (wave < q_waves(HC)) {
+#pragma unroll
+        for (int s = 0; s < kMaxA / 4; ++s)
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt) {
+                const int k = 4 * s + kq;
+                wa[s][tt] = k < q.A ? q.cp[(size_t)(col0 + 16 * tt + c16) * in + q.D + k] : 0.0f;
+            }
+    }
+}
+
+// One pass over c_net on the 16 rows of the workgroup, in the order include/guardx_usl.h fixes.  On entry (after a
+// barrier): P = the first layer's pre-activation over the observation columns, c_net's parts staged, and with ACT the
+// rows' actions in lds[L.act] and wa from q_load_wa.  ACT: the first layer adds the A action terms on top of P (without
+// it: none, h1 = tanh(P)).  bwd (workgroup-uniform): the backward GEMM against (1 - h2^2) w3, the (1 - h1^2) scale and
+// the A output sums, which leave g~ in lds[L.gt].  On exit (after a barrier): z3 in lds[L.z3].  Whole-workgroup call.
+template <int HC, bool ACT>
+GX_D void q_pass(float* lds, const QLds& L, float* H1, float* H2, const QArgs& q, const float (&wa)[kMaxA / 4][q_tiles(HC)],
+                 bool bwd, int tid)
+{
+    constexpr int HS = HC + 4, TT = q_tiles(HC), LB = TT == 2 ? 4 : kLB;
+    const int NW = q_waves(HC);
+    const int wave = tid >> 6, lw = tid & 63, c16 = lw & 15, kq = lw >> 4;
+    const int A = q.A, in = q.D + A;
+    const float* hd = lds + L.head;
+    const float* b2 = hd + HC;
+    const float* w3 = hd + 2 * HC;
+    const float* P = lds + L.P;
+    const float* act = lds + L.act;
+    float* gt = lds + L.gt;
+    float* z3 = lds + L.z3;
+    const float* gW2 = q.cp + (size_t)HC * in + HC;
+    const float* Bf = HC == 64 ? lds + L.Wt2 : q.cwt + (size_t)pad4(q.D) * HC; // forward: [k][unit]
+    const float* Bb = HC == 64 ? lds + L.W2 : gW2;                             // backward: [unit j][k]
+    const int col0 = 16 * TT * wave;
+
+    // first layer: P, then (ACT) the A action terms on top of it; tanh
+    if (wave < NW) {
+        mfma_f4 acc[TT];
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[tt][r] = P[(4 * kq + r) * HS + col0 + 16 * tt + c16];
+        if constexpr (ACT) {
+#pragma unroll
+            for (int s = 0; s < kMaxA / 4; ++s)
+                if (4 * s < A) {
+                    const float av = act[c16 * kAS + 4 * s + kq];
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wa[s][tt], acc[tt], 0, 0, 0);
+                }
+        }
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) H1[(4 * kq + r) * HS + col0 + 16 * tt + c16] = tanh_f(acc[tt][r]);
+    }
+    wg_sync_lds();
+    // second layer
+    if (wave < NW) {
+        mfma_f4 acc[TT];
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) { const float bb = b2[col0 + 16 * tt + c16]; acc[tt] = mfma_f4{bb, bb, bb, bb}; }
+        q_chain<TT, false, LB>(acc, Bf, HC, col0, H1, HS, w3, HC, c16, kq);
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) H2[(4 * kq + r) * HS + col0 + 16 * tt + c16] = tanh_f(acc[tt][r]);
+    }
+    wg_sync_lds();
+    // the head (row e on the 16 lanes of tid = 16 e ..), and the backward GEMM, which does not wait for it
+    if (tid < 16 * kEnv) {
+        const int e = tid >> 4, l = tid & 15;
+        const float z = hd[3 * HC] + dot16<HC>(w3, H2 + e * HS, l);
+        if (l == 0) z3[e] = z;
+    }
+    if (bwd && wave < NW) {
+        mfma_f4 acc[TT];
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) acc[tt] = mfma_f4{0.0f, 0.0f, 0.0f, 0.0f};
+        q_chain<TT, true, LB>(acc, Bb, HC, col0, H2, HS, w3, HC, c16, kq);
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { // g1 in place of h1: every element is read and written by its own lane alone
+                float* p = H1 + (4 * kq + r) * HS + col0 + 16 * tt + c16;
+                const float h = *p;
+                *p = __fmul_rn(__fsub_rn(1.0f, __fmul_rn(h, h)), acc[tt][r]);
+            }
+    }
+    wg_sync_lds();
+    // the A output sums: task (row e, component i) on 16 lanes
+    if (bwd) {
+        const int l = tid & 15;
+        for (int task = tid >> 4; task < kEnv * A; task += kThreads / 16) {
+            const int e = task / A, i = task - e * A;
+            const float g = dot16<HC>(lds + L.W1a + i * HC, H1 + e * HS, l);
+            if (l == 0) gt[e * kAS + i] = g;
+        }
+        wg_sync_lds();
+    }
 }
 
 } // namespace

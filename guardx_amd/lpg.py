@@ -24,9 +24,6 @@ import ctypes as C
 import torch
 
 from . import _closed_loop as _cl, _lpg_native
-from .critic import HIDDEN
-from ._closed_loop import q_floats
-from .usl import Q_CRITIC_ATTR
 
 
 def projection_probe(q_critic, obs, act, q_init, delta=0.0, grad_scale=1.0, step_sign=1.0):
@@ -34,28 +31,11 @@ def projection_probe(q_critic, obs, act, q_init, delta=0.0, grad_scale=1.0, step
     act (n, A) and q_init (n,) float32 device tensors -> dict a_safe (n, A), q (n,) [Q(obs, act)], G (n, A) [the scaled
     gradient at the zero action, every row], lam (n,) [0 for branch 0], branch (n,) int32 [0 q <= delta, 1 corrected
     with lam > 0, 2 corrected with lam clipped to 0 or NaN]"""
-    for t in (q_critic, obs, act, q_init):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise ValueError("projection_probe: q_critic, obs, act and q_init must be float32 device tensors")
-    if obs.dim() != 2 or act.dim() != 2 or obs.shape[0] != act.shape[0] or tuple(q_init.shape) != (obs.shape[0],):
-        raise ValueError("projection_probe: obs must be (n, D), act (n, A) and q_init (n,)")
-    n, D = obs.shape
-    A = act.shape[1]
-    if n >= 2 ** 31:
-        raise ValueError("projection_probe: more than 2^31 - 1 rows")
-    if getattr(q_critic, Q_CRITIC_ATTR, D + A) != D + A:
-        raise ValueError(f"projection_probe: q_critic reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs, obs and act have {D} + {A}")
-    hc = _cl.q_hidden(q_critic.numel(), D, A)
-    if hc is None:
-        raise ValueError(f"q_critic has {q_critic.numel()} floats; expected one of {[q_floats(D, A, h) for h in HIDDEN]} "
-                         f"(hidden {HIDDEN}) for {D} + {A} inputs")
-    cp, obs, act, q_init = q_critic.contiguous(), obs.contiguous(), act.contiguous(), q_init.contiguous()
+    cp, obs, act, n, D, A, hc = _cl.q_probe_inputs("projection_probe", q_critic, obs, act, extra=(("q_init", q_init),))
+    q_init = q_init.contiguous()
     lib = _lpg_native.load()
     dev = obs.device
-    nw = int(lib.gxp_probe_work_floats(D, A, hc))
-    if nw < 0:
-        raise NotImplementedError(f"projection_probe supports an even action width <= 16, not {A}")
-    work = torch.empty(nw, dtype=torch.float32, device=dev)
+    work = _cl.q_probe_work("projection_probe", int(lib.gxp_probe_work_floats(D, A, hc)), A, dev)
     out = dict(a_safe=torch.empty_like(act), q=torch.empty(n, dtype=torch.float32, device=dev),
                G=torch.empty_like(act), lam=torch.empty(n, dtype=torch.float32, device=dev),
                branch=torch.empty(n, dtype=torch.int32, device=dev))
@@ -78,24 +58,13 @@ class State(_cl.State):
 
 def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0, store_init=True,
             grad_scale=None, step_sign=1.0):
-    obs0, N, D, A, T = _cl.begin(env, "rollout_lpg", obs0, T)
-    if q_critic is None or not torch.is_tensor(q_critic) or getattr(q_critic, Q_CRITIC_ATTR, None) is None:
-        raise ValueError("rollout_lpg needs q_critic=Engine.pack_q_critic(ac.ccritic, device=...) (the "
-                         "declaration travels with the tensor pack_q_critic returns, not with copies of it)")
-    params, cp, obs0, hidden = _cl.device_inputs(env, params, q_critic, obs0, D, A)
-    c_hidden = _cl.q_hidden(cp.numel(), D, A)
-    if c_hidden is None or getattr(q_critic, Q_CRITIC_ATTR) != D + A:
-        raise ValueError(f"q_critic has {cp.numel()} floats and reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs; expected "
-                         f"one of {[q_floats(D, A, h) for h in HIDDEN]} (hidden {HIDDEN}) for {D} + {A} inputs")
+    params, cp, obs0, N, D, A, T, hidden, c_hidden = _cl.q_rollout_inputs(env, "rollout_lpg", params, q_critic, obs0, T)
     lib = _lpg_native.load()
     st = env._lpg
     if st is None:
         st = env._lpg = State(env)
-    new = env._new
-    out = dict(obs=new(T, N, D), act=new(T, N, A), act_safe=new(T, N, A), mu=new(T, N, A),
-               logp=new(T, N), val=new(T, N), qc=new(T, N), lam=new(T, N), rew=new(T, N), cost=new(T, N),
-               done=new(T, N), obs_last=new(N, D), val_last=new(N), logstd=new(A))
-    work = new(int(lib.gxp_work_floats(D, A, hidden, c_hidden)))
+    out = _cl.q_rollout_out(env, T, N, D, A, 'lam')
+    work = env._new(int(lib.gxp_work_floats(D, A, hidden, c_hidden)))
     a = _lpg_native.GxpStepArgs()
     _cl.fill(a, env, st, out, T, noise_seed, params, work, obs0)
     a.D, a.hidden, a.c_hidden = D, hidden, c_hidden

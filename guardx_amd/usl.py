@@ -20,11 +20,7 @@ import ctypes as C
 import torch
 
 from . import _closed_loop as _cl, _usl_native
-from ._closed_loop import policy_floats, q_floats  # noqa: F401 (part of this module's surface)
-from .critic import HIDDEN
-
-# how pack_q_critic marks what it returns: c_net's input width, checked against D + A at the call
-Q_CRITIC_ATTR = "gx_q_critic"
+from ._closed_loop import Q_CRITIC_ATTR, policy_floats, q_floats  # noqa: F401 (part of this module's surface)
 
 
 def pack_q_critic(ccritic, device=None):
@@ -54,30 +50,12 @@ def correction_probe(q_critic, obs, act, delta=0.0, niter=20, eta=0.05, grad_sca
     and act (n, A) float32 device tensors -> dict a_safe (n, A), q0 (n,), grad0 (n, A) [the scaled gradient of the first
     pass, 0 for a row that stops before it], iters (n,) int32 [updates applied], stop (n,) int32 [0 niter exhausted,
     1 max a > 1, 2 q <= delta]"""
-    for t in (q_critic, obs, act):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise ValueError("correction_probe: q_critic, obs and act must be float32 device tensors")
-    if obs.dim() != 2 or act.dim() != 2 or obs.shape[0] != act.shape[0]:
-        raise ValueError("correction_probe: obs must be (n, D) and act (n, A)")
+    cp, obs, act, n, D, A, hc = _cl.q_probe_inputs("correction_probe", q_critic, obs, act)
     if int(niter) < 0:
         raise ValueError("correction_probe: niter must be >= 0")
-    n, D = obs.shape
-    A = act.shape[1]
-    if n >= 2 ** 31:
-        raise ValueError("correction_probe: more than 2^31 - 1 rows")
-    if getattr(q_critic, Q_CRITIC_ATTR, D + A) != D + A:
-        raise ValueError(f"correction_probe: q_critic reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs, obs and act have {D} + {A}")
-    hc = _cl.q_hidden(q_critic.numel(), D, A)
-    if hc is None:
-        raise ValueError(f"q_critic has {q_critic.numel()} floats; expected one of {[q_floats(D, A, h) for h in HIDDEN]} "
-                         f"(hidden {HIDDEN}) for {D} + {A} inputs")
-    cp, obs, act = q_critic.contiguous(), obs.contiguous(), act.contiguous()
     lib = _usl_native.load()
     dev = obs.device
-    nw = int(lib.gxu_probe_work_floats(D, A, hc))
-    if nw < 0:
-        raise NotImplementedError(f"correction_probe supports an even action width <= 16, not {A}")
-    work = torch.empty(nw, dtype=torch.float32, device=dev)
+    work = _cl.q_probe_work("correction_probe", int(lib.gxu_probe_work_floats(D, A, hc)), A, dev)
     out = dict(a_safe=torch.empty_like(act), q0=torch.empty(n, dtype=torch.float32, device=dev),
                grad0=torch.empty_like(act), iters=torch.empty(n, dtype=torch.int32, device=dev),
                stop=torch.empty(n, dtype=torch.int32, device=dev))
@@ -94,27 +72,16 @@ State = _cl.State
 
 def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0, niter=20, eta=0.05,
             grad_scale=None):
-    obs0, N, D, A, T = _cl.begin(env, "rollout_usl", obs0, T)
+    params, cp, obs0, N, D, A, T, hidden, c_hidden = _cl.q_rollout_inputs(env, "rollout_usl", params, q_critic, obs0, T)
     niter = int(niter)
     if niter < 0:
         raise ValueError("rollout_usl: niter must be >= 0")
-    if q_critic is None or not torch.is_tensor(q_critic) or getattr(q_critic, Q_CRITIC_ATTR, None) is None:
-        raise ValueError("rollout_usl needs q_critic=Engine.pack_q_critic(ac.ccritic, device=...) (the "
-                         "declaration travels with the tensor pack_q_critic returns, not with copies of it)")
-    params, cp, obs0, hidden = _cl.device_inputs(env, params, q_critic, obs0, D, A)
-    c_hidden = _cl.q_hidden(cp.numel(), D, A)
-    if c_hidden is None or getattr(q_critic, Q_CRITIC_ATTR) != D + A:
-        raise ValueError(f"q_critic has {cp.numel()} floats and reads {getattr(q_critic, Q_CRITIC_ATTR)} inputs; expected "
-                         f"one of {[q_floats(D, A, h) for h in HIDDEN]} (hidden {HIDDEN}) for {D} + {A} inputs")
     lib = _usl_native.load()
     st = env._usl
     if st is None:
         st = env._usl = State(env)
-    new = env._new
-    out = dict(obs=new(T, N, D), act=new(T, N, A), act_safe=new(T, N, A), mu=new(T, N, A),
-               logp=new(T, N), val=new(T, N), qc=new(T, N), iters=new(T, N), rew=new(T, N), cost=new(T, N),
-               done=new(T, N), obs_last=new(N, D), val_last=new(N), logstd=new(A))
-    work = new(int(lib.gxu_work_floats(D, A, hidden, c_hidden)))
+    out = _cl.q_rollout_out(env, T, N, D, A, 'iters')
+    work = env._new(int(lib.gxu_work_floats(D, A, hidden, c_hidden)))
     a = _usl_native.GxuStepArgs()
     _cl.fill(a, env, st, out, T, noise_seed, params, work, obs0)
     a.D, a.hidden, a.c_hidden = D, hidden, c_hidden

@@ -1,0 +1,61 @@
+"""The C header of a side library (include/guardx_<key>.h, prefix gx?_) parsed into ctypes prototypes, and the
+comparison of the library's binding (guardx_amd/_<key>_native.py) with it: shared by the host suites of the usl and the
+lpg library."""
+import ctypes as C
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def header(key):
+    text = open(os.path.join(ROOT, "include", "guardx_%s.h" % key)).read()
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _ctype(decl, prefix, step_args):
+    base = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, prefix + "_status": C.c_int,
+            "float": C.c_float, "const char*": C.c_char_p, "void*": C.c_void_p, "const float*": C.c_void_p,
+            "float*": C.c_void_p, "int32_t*": C.c_void_p}
+    t = re.sub(r"\s+", " ", decl.strip())
+    t = re.sub(r"\s*\*\s*", "* ", t).strip()
+    t = re.sub(r"\s+[A-Za-z_][A-Za-z_0-9]*$", "", t) if not t.endswith("*") and " " in t else t
+    t = t.strip()
+    return C.POINTER(step_args) if t == "const %s_step_args*" % prefix else base[t]
+
+
+def prototypes(key, prefix, step_args):
+    """{name: (restype, [argtypes])} of every gx?_ function the header declares"""
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_0-9 ]+?\*?)\s*\b(%s_[a-z_0-9]+)\s*\(([^)]*)\)\s*;" % prefix, header(key)):
+        args = args.strip()
+        argt = [] if args in ("", "void") else [_ctype(a, prefix, step_args) for a in args.split(",")]
+        ret = ret.strip()
+        protos[name] = (_ctype(ret if ret.endswith("*") else ret + " x", prefix, step_args), argt)
+    return protos
+
+
+def assert_binding_matches_the_header(key, prefix, n, step_args):
+    """the 9 prototypes, the fields of gx?_step_args in order and the status values of binding module `n`"""
+    protos = prototypes(key, prefix, step_args)
+    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 9
+    for name, (res, args) in protos.items():
+        assert n.SYMBOLS[name] == (res, args), name
+    body = re.search(r"typedef struct %s_step_args \{(.*?)\} %s_step_args;" % (prefix, prefix), header(key), flags=re.S).group(1)
+    fields = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if not stmt:
+            continue
+        m = re.match(r"(const float\*|float\*|uint32_t|int32_t|float)\s+(.*)", stmt)
+        base = {"const float*": C.c_void_p, "float*": C.c_void_p, "uint32_t": C.c_uint32, "int32_t": C.c_int32,
+                "float": C.c_float}[m.group(1)]
+        for nm in m.group(2).split(","):
+            nm = nm.strip()
+            arr = re.match(r"(\w+)\[(\d+)\]", nm)
+            fields.append((arr.group(1), base * int(arr.group(2))) if arr else (nm, base))
+    assert [(f[0], f[1]) for f in step_args._fields_] == fields
+    P = prefix.upper()
+    st = dict(re.findall(r"(%s_[A-Z_]+) = (\d+)" % P, header(key)))
+    assert {k: int(v) for k, v in st.items()} == {P + "_" + k: getattr(n, P + "_" + k)
+                                                  for k in ("OK", "ERR_ARG", "ERR_UNSUPPORTED", "ERR_HIP")}

@@ -268,7 +268,7 @@ def test_probe_against_float64(name):
 # ---------------------------------------------------------------------------------------------------------------------
 # grad_scale = 8: eps = |delta - q_init| does not scale with the gradient, G . a does, so the corrected rows fall on both
 # sides of lam = 0 (with the reference's 1 / env_num almost every lam is clipped to 0)
-@pytest.mark.parametrize("robot,h,hc,delta", [("point", 64, 64, 0.6), ("ant", 256, 128, 0.3)])
+@pytest.mark.parametrize("robot,h,hc,delta", [("point", 64, 64, 0.6), ("ant", 256, 128, 0.3), ("swimmer", 128, 256, 0.0)])
 def test_rollout_equals_the_probe_and_steps_the_env_on_act_safe(robot, h, hc, delta):
     from guardx_amd import Engine
     N, T, gs = 17, 5, 8.0

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import lpg64
+import side_abi
 import usl64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,10 +31,13 @@ def test_lpg_source_hash_covers_its_sources_and_the_shared_header():
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
     have = {norm(h) for h in libs["lpg"].headers}
     incs = set()
-    for f in ("gx_lpg.hip", "gx_qcritic.h"):
+    for f in ("gx_lpg.hip", "gx_qstep.h", "gx_qcritic.h"):
         incs |= {norm(i) for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())}
-    assert incs <= have and {norm("gx_qcritic.h"), norm("gx_device.h"), norm("../../include/guardx_lpg.h")} <= have
-    assert norm("gx_qcritic.h") in {norm(h) for h in libs["usl"].headers}
+    assert incs <= have and norm("gx_qstep.h") in incs
+    assert {norm("gx_qstep.h"), norm("gx_qcritic.h"), norm("gx_device.h"), norm("../../include/guardx_lpg.h")} <= have
+    assert {norm("gx_qcritic.h"), norm("gx_qstep.h")} <= {norm(h) for h in libs["usl"].headers}
+    assert not any("qstep" in h for key, lib in libs.items() if key not in ("usl", "lpg") for h in lib.headers)
+    assert not any("qstep" in h for h in build.HEADERS + build.SOURCES)
     assert len(libs["lpg"].source_hash()) == 24
 
 
@@ -62,57 +66,14 @@ def test_the_older_build_ids_do_not_cover_the_shared_header():
     assert len(ids) == len(libs) + 1                            # all distinct
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "guardx_lpg.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-_BASE = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "gxp_status": C.c_int, "float": C.c_float,
-         "const char*": C.c_char_p, "void*": C.c_void_p, "const float*": C.c_void_p, "float*": C.c_void_p,
-         "int32_t*": C.c_void_p}
-
-
-def _ctype(decl):
-    from guardx_amd._lpg_native import GxpStepArgs
-    t = re.sub(r"\s+", " ", decl.strip())
-    t = re.sub(r"\s*\*\s*", "* ", t).strip()
-    t = re.sub(r"\s+[A-Za-z_][A-Za-z_0-9]*$", "", t) if not t.endswith("*") and " " in t else t
-    t = t.strip()
-    return C.POINTER(GxpStepArgs) if t == "const gxp_step_args*" else _BASE[t]
-
-
 def _prototypes():
-    protos = {}
-    for ret, name, args in re.findall(r"([A-Za-z_0-9 ]+?\*?)\s*\b(gxp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", _header()):
-        args = args.strip()
-        argt = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
-        protos[name] = (_ctype(ret.strip() + " x") if not ret.strip().endswith("*") else _ctype(ret), argt)
-    return protos
+    from guardx_amd._lpg_native import GxpStepArgs
+    return side_abi.prototypes("lpg", "gxp", GxpStepArgs)
 
 
 def test_binding_matches_the_header():
     from guardx_amd import _lpg_native as n
-    protos = _prototypes()
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 9
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    body = re.search(r"typedef struct gxp_step_args \{(.*?)\} gxp_step_args;", _header(), flags=re.S).group(1)
-    fields = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        m = re.match(r"(const float\*|float\*|uint32_t|int32_t|float)\s+(.*)", stmt)
-        base = {"const float*": C.c_void_p, "float*": C.c_void_p, "uint32_t": C.c_uint32, "int32_t": C.c_int32,
-                "float": C.c_float}[m.group(1)]
-        for nm in m.group(2).split(","):
-            nm = nm.strip()
-            arr = re.match(r"(\w+)\[(\d+)\]", nm)
-            fields.append((arr.group(1), base * int(arr.group(2))) if arr else (nm, base))
-    assert [(f[0], f[1]) for f in n.GxpStepArgs._fields_] == fields
-    st = dict(re.findall(r"(GXP_[A-Z_]+) = (\d+)", _header()))
-    assert {k: int(v) for k, v in st.items()} == {"GXP_OK": n.GXP_OK, "GXP_ERR_ARG": n.GXP_ERR_ARG,
-                                                 "GXP_ERR_UNSUPPORTED": n.GXP_ERR_UNSUPPORTED, "GXP_ERR_HIP": n.GXP_ERR_HIP}
+    side_abi.assert_binding_matches_the_header("lpg", "gxp", n, n.GxpStepArgs)
 
 
 @pytest.fixture(scope="module")

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.trpo_buffer_np import TRPOBufferNP
+import side_abi
 import usl64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,10 +59,14 @@ def test_usl_source_hash_covers_its_sources_and_leaves_the_older_libraries_alone
     from guardx_amd import build
     libs = build.LIBRARIES
     assert libs["usl"].sources == ["gx_usl.hip"]
-    incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_usl.hip")).read())
+    incs = [i for f in ("gx_usl.hip", "gx_qstep.h", "gx_qcritic.h")
+            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
     have = {norm(h) for h in libs["usl"].headers}
-    assert {norm(i) for i in incs} <= have and norm("gx_device.h") in have
+    assert {norm(i) for i in incs} <= have and {norm("gx_device.h"), norm("gx_qcritic.h"), norm("gx_qstep.h")} <= have
+    assert "gx_qstep.h" in incs and norm("gx_qstep.h") in {norm(h) for h in libs["lpg"].headers}
+    assert not any("qstep" in h for key, lib in libs.items() if key not in ("usl", "lpg") for h in lib.headers)
+    assert not any("qstep" in h for h in build.HEADERS + build.SOURCES)
     older = set(build.SOURCES) | set(libs["critic"].sources) | set(libs["statewise"].sources) | set(libs["safelayer"].sources)
     assert not (set(libs["usl"].sources) & older)
     assert all("usl" not in h for h in build.HEADERS + libs["critic"].headers + libs["statewise"].headers + libs["safelayer"].headers)
@@ -72,57 +77,14 @@ def test_usl_source_hash_covers_its_sources_and_leaves_the_older_libraries_alone
     assert len(ids) == 5 and len(libs["usl"].source_hash()) == 24
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "guardx_usl.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-_BASE = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "gxu_status": C.c_int, "float": C.c_float,
-         "const char*": C.c_char_p, "void*": C.c_void_p, "const float*": C.c_void_p, "float*": C.c_void_p,
-         "int32_t*": C.c_void_p}
-
-
-def _ctype(decl):
-    from guardx_amd._usl_native import GxuStepArgs
-    t = re.sub(r"\s+", " ", decl.strip())
-    t = re.sub(r"\s*\*\s*", "* ", t).strip()
-    t = re.sub(r"\s+[A-Za-z_][A-Za-z_0-9]*$", "", t) if not t.endswith("*") and " " in t else t
-    t = t.strip()
-    return C.POINTER(GxuStepArgs) if t == "const gxu_step_args*" else _BASE[t]
-
-
 def _prototypes():
-    protos = {}
-    for ret, name, args in re.findall(r"([A-Za-z_0-9 ]+?\*?)\s*\b(gxu_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", _header()):
-        args = args.strip()
-        argt = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
-        protos[name] = (_ctype(ret.strip() + " x") if not ret.strip().endswith("*") else _ctype(ret), argt)
-    return protos
+    from guardx_amd._usl_native import GxuStepArgs
+    return side_abi.prototypes("usl", "gxu", GxuStepArgs)
 
 
 def test_binding_matches_the_header():
     from guardx_amd import _usl_native as n
-    protos = _prototypes()
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 9
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    body = re.search(r"typedef struct gxu_step_args \{(.*?)\} gxu_step_args;", _header(), flags=re.S).group(1)
-    fields = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        m = re.match(r"(const float\*|float\*|uint32_t|int32_t|float)\s+(.*)", stmt)
-        base = {"const float*": C.c_void_p, "float*": C.c_void_p, "uint32_t": C.c_uint32, "int32_t": C.c_int32,
-                "float": C.c_float}[m.group(1)]
-        for nm in m.group(2).split(","):
-            nm = nm.strip()
-            arr = re.match(r"(\w+)\[(\d+)\]", nm)
-            fields.append((arr.group(1), base * int(arr.group(2))) if arr else (nm, base))
-    assert [(f[0], f[1]) for f in n.GxuStepArgs._fields_] == fields
-    st = dict(re.findall(r"(GXU_[A-Z_]+) = (\d+)", _header()))
-    assert {k: int(v) for k, v in st.items()} == {"GXU_OK": n.GXU_OK, "GXU_ERR_ARG": n.GXU_ERR_ARG,
-                                                 "GXU_ERR_UNSUPPORTED": n.GXU_ERR_UNSUPPORTED, "GXU_ERR_HIP": n.GXU_ERR_HIP}
+    side_abi.assert_binding_matches_the_header("usl", "gxu", n, n.GxuStepArgs)
 
 
 @pytest.fixture(scope="module")
