@@ -67,9 +67,12 @@ LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 # Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
 # libguardx_hip.so -- and the profiles taken on that build -- alone.
 _SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
-# c_net's device code and the step libraries' shared front end and host side, shared by the two learners that correct the
-# action with a Q critic (and by them alone: the older libraries' build ids do not cover them)
-_Q_HEADERS = _SIDE_HEADERS + ["gx_qcritic.h", "gx_qstep.h"]
+# what the four step libraries share (sizes, the transpose kernel, the MFMA chain, the sample / log-prob block, the host
+# side's checks, dispatch and launches): not the critic library's, whose build id does not cover it
+_STEP_HEADERS = _SIDE_HEADERS + ["gx_step.h"]
+# c_net's device code and the front end of its step and probe kernels, shared by the two learners that correct the action
+# with a Q critic (and by them alone: the other libraries' build ids do not cover them)
+_Q_HEADERS = _STEP_HEADERS + ["gx_qcritic.h", "gx_qstep.h"]
 
 
 class SideLibrary:
@@ -107,8 +110,8 @@ class SideLibrary:
 
 LIBRARIES = {lib.key: lib for lib in (
     SideLibrary("critic", "GXC_BUILD_ID", ["gx_critic.hip"], _SIDE_HEADERS),
-    SideLibrary("statewise", "GXS_BUILD_ID", ["gx_statewise.hip"], _SIDE_HEADERS),
-    SideLibrary("safelayer", "GXL_BUILD_ID", ["gx_safelayer.hip"], _SIDE_HEADERS),
+    SideLibrary("statewise", "GXS_BUILD_ID", ["gx_statewise.hip"], _STEP_HEADERS),
+    SideLibrary("safelayer", "GXL_BUILD_ID", ["gx_safelayer.hip"], _STEP_HEADERS),
     SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _Q_HEADERS),
     SideLibrary("lpg", "GXP_BUILD_ID", ["gx_lpg.hip"], _Q_HEADERS),
 )}

@@ -15,8 +15,9 @@
 // sums: G).  One lane per row then projects.  At h_c = 64 both layouts of W2 live in LDS; wider ones are streamed from L2.
 //
 // Here: the two passes' sequence, the per-row projection, the two kernels and the C entry points.  The pass itself is
-// gx_qcritic.h:q_pass, the one USL's iteration runs; the step kernel's front end, the probe kernel's, the LDS layouts
-// and the host side's checks, dispatch and launches are gx_qstep.h's, shared with gx_usl.hip.
+// gx_qcritic.h:q_pass, the one USL's iteration runs; the step kernel's front end, the probe kernel's and the LDS layouts
+// are gx_qstep.h's, shared with gx_usl.hip; the sample / log-prob block, the MFMA chain and the host side's checks,
+// dispatch and launches are gx_step.h's, shared with every step library.
 #include "../../include/guardx_lpg.h"
 #include "gx_qstep.h"
 
@@ -191,7 +192,7 @@ extern "C" gxp_status gxp_policy_step(const gxp_step_args* g, void* stream)
     a.sign = g->step_sign;
     a.q_init = g->d_q_init;
     a.lam = a.c.tail ? nullptr : g->d_lam + tn;
-    return q_launch(fail, "gxp_policy_step", q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, a,
+    return q_launch(fail, "gxp_policy_step", q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, kThreads, a,
                     step_lds_bytes(g->D, g->A, g->hidden, g->c_hidden), stream);
 }
 

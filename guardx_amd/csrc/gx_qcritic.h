@@ -1,28 +1,21 @@
 // gx_qcritic.h -- the cost critic Q(obs, act) = Softplus(c_net(cat(obs, act))) of the USL and the LPG learners as device
 // code, for gx_usl.hip and gx_lpg.hip (through gx_qstep.h, which holds what their step and probe kernels and their host
-// sides share).  The 16-env / 768-thread workgroup's constants, c_net's part of the LDS and its staging, Softplus and its
-// derivative, the MFMA chains of the hidden layers (forward, and backward against (1 - h2^2) w3), the 16-lane output
-// sums, q_pass -- one forward pass over c_net, with or without the action terms and the backward pass: every trip of
-// USL's iteration and both of LPG's passes -- and the kernel that transposes the hidden layers into a path's workspace.
+// sides share).  The 768-thread workgroup, c_net's part of the LDS and its staging, Softplus' derivative, the 16-lane
+// output sums and q_pass -- one forward pass over c_net, with or without the action terms and the backward pass: every
+// trip of USL's iteration and both of LPG's passes.  Softplus, the MFMA chains of the hidden layers (forward, and backward
+// against (1 - h2^2) w3) and the kernel that transposes the hidden layers into a path's workspace are gx_step.h's.
 // The operation order of every function here is the one include/guardx_usl.h fixes; include/guardx_lpg.h refers to it.
 // One translation unit per library: everything sits in an unnamed namespace.
 #ifndef GX_QCRITIC_H
 #define GX_QCRITIC_H
-#include "gx_policy.h"
-#include <hip/hip_runtime.h>
+#include "gx_step.h"
 
 namespace {
 
 using namespace gx;
 
-constexpr int kEnv = 16;       // envs per workgroup
 constexpr int kThreads = 768;  // 12 waves
-constexpr int kMaxA = 16;
 constexpr int kAS = kMaxA + 1; // LDS row stride of the per-row action arrays
-
-GX_HD int64_t net_floats(int D, int Out, int H) { return (int64_t)H * D + H + (int64_t)H * H + H + (int64_t)Out * H + Out; }
-
-GX_HD int64_t wt_floats(int D, int H) { return (int64_t)pad4(D) * H + (int64_t)H * H; }
 
 // waves that share c_net's unit tiles in a pass, and tiles per wave
 GX_HD int q_waves(int HC) { return HC == 256 ? 8 : HC / 16; }
@@ -48,48 +41,12 @@ GX_HD QLds q_lds_layout(int A, int HC, int base)
     return L;
 }
 
-// Softplus as torch evaluates it (beta = 1, threshold = 20), in the statewise path's form (gx_statewise.hip:softplus_f):
-// x > 20 ? x : max(x, 0) + log1p(exp(-|x|)), log1p(u) = log(w) u / (w - 1) with w = fl(1 + u), u itself once w == 1.
-GX_D float softplus_f(float x)
-{
-    if (x > 20.0f) return x;
-    const float u = exp_f(-fabsf(x));
-    const float w = 1.0f + u;
-    const float l1p = (w == 1.0f) ? u : log_f(w) * (u / (w - 1.0f));
-    return (x > 0.0f ? x : 0.0f) + l1p;
-}
-// its derivative as torch's backward evaluates it
+// the derivative of Softplus (gx_step.h:softplus_f) as torch's backward evaluates it
 GX_D float softplus_grad_f(float x)
 {
     if (x > 20.0f) return 1.0f;
     const float e = exp_f(x);
     return __fdiv_rn(e, __fadd_rn(e, 1.0f));
-}
-
-// wt = [pi Wt1 | pi Wt2 | v Wt1 | v Wt2 | c Wt1 | c Wt2]; Wt1 [pad4 D][h] (rows D .. zero; c_net: its D observation
-// columns), Wt2 [h][h], from the torch layout W1 [h][in] b1 W2 [h][h] ...  first = 2: c_net alone (the probe).
-__global__ void usl_transpose_kernel(const float* __restrict__ params, const float* __restrict__ cp, float* __restrict__ wt,
-                                     int D, int A, int H, int HC, int first)
-{
-    const int Dp = pad4(D);
-    const long long per = (long long)Dp * H + (long long)H * H, perc = (long long)Dp * HC + (long long)HC * HC;
-    const long long skip = first == 2 ? 2 * per : 0, n = 2 * per + perc - skip;
-    for (long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += (long long)gridDim.x * blockDim.x) {
-        const long long i = i0 + skip;
-        const int net = i < per ? 0 : (i < 2 * per ? 1 : 2);
-        const long long r = i - (long long)net * per;
-        const int h = net == 2 ? HC : H, in = net == 2 ? D + A : D;
-        const float* g = net == 0 ? params : (net == 1 ? params + net_floats(D, A, H) : cp);
-        const long long n1 = (long long)Dp * h;
-        if (r < n1) {
-            const int k = (int)(r / h), j = (int)(r - (long long)k * h);
-            wt[i0] = k < D ? g[(size_t)j * in + k] : 0.0f;
-        } else {
-            const long long r2 = r - n1;
-            const int k = (int)(r2 / h), j = (int)(r2 - (long long)k * h);
-            wt[i0] = g[(size_t)h * in + h + (size_t)j * h + k];
-        }
-    }
 }
 
 // what the iteration needs besides LDS
@@ -99,74 +56,6 @@ struct QArgs {
     const float* cp;   // c_net as packed
     const float* cwt;  // its [pad4 D][HC] first-layer observation block and [HC][HC] second layer, transposed
 };
-
-// acc[tile] += A[16 envs][K] * B[K][16 units of the tile], k ascending (the order of the fmaf chain); tile tt holds the
-// units col0 + 16 tt + c16.  The operands of kLB k-steps are fetched together and one block AHEAD of the MFMAs that
-// consume them (two register sets, the loop advances by two blocks).  BWD: the A operand is built on the way in,
-// d2[j] = (1 - h2[j] h2[j]) w3[j] from the activation row and the head's weights.
-constexpr int kLB = 8;
-template <int TT, bool BWD, int LB>
-GX_D void q_fetch(float (&av)[LB], float (&bv)[LB][TT], const float* ap, const float* w3p, const float* bp, int ldb, int s0, int ns)
-{
-#pragma unroll
-    for (int i = 0; i < LB; ++i) {
-        const int sidx = s0 + i;
-        if (sidx < ns) { // wave-uniform
-            float x = ap[4 * sidx];
-            if (BWD) x = __fmul_rn(__fsub_rn(1.0f, __fmul_rn(x, x)), w3p[4 * sidx]);
-            av[i] = x;
-#pragma unroll
-            for (int tt = 0; tt < TT; ++tt) bv[i][tt] = bp[(size_t)(4 * sidx) * ldb + 16 * tt];
-        }
-    }
-}
-template <int TT, int LB>
-GX_D void q_issue(mfma_f4 (&acc)[TT], const float (&av)[LB], const float (&bv)[LB][TT], int s0, int ns)
-{
-#pragma unroll
-    for (int i = 0; i < LB; ++i)
-        if (s0 + i < ns) {
-#pragma unroll
-            for (int tt = 0; tt < TT; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[i][tt], acc[tt], 0, 0, 0);
-        }
-}
-// Ain: activation rows [16][AS]; B: [K][ldb], this wave's tiles starting at column col0.  LB: k-steps per block (fewer
-// where two tiles per wave and the iteration's own state leave fewer registers)
-template <int TT, bool BWD, int LB = kLB>
-GX_D void q_chain(mfma_f4 (&acc)[TT], const float* B, int ldb, int col0, const float* Ain, int AS, const float* w3, int K,
-                  int c16, int kq)
-{
-    const int ns = K >> 2;
-    const float* ap = Ain + c16 * AS + kq;
-    const float* wp = w3 + kq;
-    const float* bp = B + (size_t)kq * ldb + col0 + c16;
-    float a0[LB], b0[LB][TT], a1[LB], b1[LB][TT];
-    q_fetch<TT, BWD, LB>(a0, b0, ap, wp, bp, ldb, 0, ns);
-#pragma unroll 1
-    for (int s0 = 0; s0 < ns; s0 += 2 * LB) {
-        q_fetch<TT, BWD, LB>(a1, b1, ap, wp, bp, ldb, s0 + LB, ns);
-        q_issue<TT, LB>(acc, a0, b0, s0, ns);
-        q_fetch<TT, BWD, LB>(a0, b0, ap, wp, bp, ldb, s0 + 2 * LB, ns);
-        q_issue<TT, LB>(acc, a1, b1, s0 + LB, ns);
-    }
-}
-
-// one hidden layer of this wave's tiles: acc = bias, chain over k ascending; TANH: tanh into the activation rows,
-// otherwise the pre-activation itself (c_net's first layer before its action columns)
-template <int TT, bool TANH>
-GX_D void hidden_layer(const float* bias, const float* __restrict__ wt, int Hn, int col0, const float* Ain, int AS, int K,
-                       float* out, int c16, int kq)
-{
-    mfma_f4 acc[TT];
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt) { const float bb = bias[col0 + 16 * tt + c16]; acc[tt] = mfma_f4{bb, bb, bb, bb}; }
-    q_chain<TT, false>(acc, wt, Hn, col0, Ain, AS, Ain, K, c16, kq);
-    float* o = out + col0 + c16;
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[(4 * kq + r) * (Hn + 4) + 16 * tt] = TANH ? tanh_f(acc[tt][r]) : acc[tt][r];
-}
 
 // c_net's first layer over the observation columns, this wave's quarter of the units, at most two tiles at a time (the
 // iteration's own registers stay live around it)

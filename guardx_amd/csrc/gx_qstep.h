@@ -1,15 +1,12 @@
 // gx_qstep.h -- what the step libraries of the learners with a Q critic (gx_usl.hip, gx_lpg.hip) share besides c_net
-// itself (gx_qcritic.h): the LDS layouts of the step and the probe kernel, the fields both StepArgs have, the front end
-// of the step kernel (ac.step on the observation row, up to the sampled action) and of the probe kernel, and the host
-// side -- sizes, shape checks, kernel dispatch, the checks and the row-block arithmetic of gx?_policy_step, the launches.
-// The host functions are templates over the library's status enum (the two enums have equal values) and its public
-// gx?_step_args (equal names for every shared field); they report through the library's own `fail`, passed first.
+// itself (gx_qcritic.h) and what every step library shares (gx_step.h): the LDS layouts of the step and the probe kernel,
+// the fields both StepArgs have, the front end of the step kernel (ac.step on the observation row, up to the sampled
+// action) and of the probe kernel, and on the host the sizes, the probe's run and gx_step.h's prepare, checks and
+// row-block arithmetic with c_net's own arguments filled in.  The host functions are templates like gx_step.h's.
 // One translation unit per library: everything sits in an unnamed namespace.
 #ifndef GX_QSTEP_H
 #define GX_QSTEP_H
 #include "gx_qcritic.h"
-#include <algorithm>
-#include <string>
 
 namespace {
 
@@ -49,26 +46,18 @@ GX_HD Lds probe_lds_layout(int D, int A, int HC)
     return L;
 }
 
-// what both kernels' views of a gx?_step_args hold: this step's row blocks resolved on the host
-struct QStepCommon {
-    int N, env_offset;
-    int tail, prologue;
-    uint32_t seed0, seed1, tnoise;
+// what both step kernels' views of a gx?_step_args hold
+struct QStepCommon : StepCommon {
     QArgs q;
-    const float *params, *wt;
-    const float* obs_rd;              // [N][D]
-    const float *rew_in, *cost_in, *done_in;
-    float *rew_p, *cost_p, *done_p;                               // row block t - 1
-    float *obs, *act, *act_safe, *mu, *logp, *val, *qc, *logstd;  // row block t (tail: obs_last, val_last)
+    float *act_safe, *qc; // row block t
 };
 
 // The front end of a step kernel, `ac.step(o)` on the 16 rows of the workgroup: the heads and c_net's parts staged, the
 // prologue's copies, the X tile written through to obs, the two hidden layers of the actor and the critic beside c_net's
 // first layer over the observation columns (P), the output tasks, the value, the noise, the action, log pi(a | o) and
 // logstd.  Returns true in the tail (the caller returns); otherwise after the barrier that hands U to c_net, with the
-// sampled actions in lds[L.q.act].  Whole-workgroup call.  The Gaussian sample / log-prob block is
-// gx_policy_step.hip:policy_step_tail's and is written out at four sites: there, in gx_statewise.hip, in
-// gx_safelayer.hip and here (five while gx_usl.hip and gx_lpg.hip each held this front end).
+// sampled actions in lds[L.q.act].  Whole-workgroup call.  The Gaussian sample / log-prob block is gx_step.h:sample_row,
+// the side libraries' one copy of gx_policy_step.hip:policy_step_tail's (two sites in all, where there were four).
 template <int H, int HC>
 GX_D bool q_step_front(float* lds, const Lds& L, const QStepCommon& a, int tid)
 {
@@ -132,38 +121,16 @@ GX_D bool q_step_front(float* lds, const Lds& L, const QStepCommon& a, int tid)
     }
     wg_sync_lds();
     // per env: the value, and (not in the tail) the noise, the action and log pi(a | o) of ac.step
-    // (gx_policy_step.hip:policy_step_tail)
     const float* gls = a.params + msz_pi + msz_v;
     if (tid < kEnv) {
         const int e = tid, env = env0 + e;
         if (env < a.N) {
-            const float* oe = outs + e * OS;
-            a.val[env] = oe[A];
-            if (!a.tail) {
-                float lp = 0.0f;
-                for (int pr = 0; 2 * pr < A; ++pr) { // one counter per pair of action dimensions
-                    float z[2];
-                    normal_pair(a.seed0, a.seed1, (uint32_t)(a.env_offset + env), a.tnoise * 16u + (uint32_t)pr, z[0], z[1]);
-                    for (int q = 0; q < 2; ++q) {
-                        const int d = 2 * pr + q;
-                        const float sd = exp_f(gls[d]);
-                        const float lsd = log_f(sd);
-                        const float m = oe[d];
-                        const float act = fmaf(sd, z[q], m);
-                        const float df = act - m;
-                        const float var = sd * sd;
-                        lp = lp + ((-(df * df) / (2.0f * var) - lsd) - 0.9189385332046727f);
-                        a.act[(size_t)env * A + d] = act;
-                        a.mu[(size_t)env * A + d] = m;
-                        lds[L.q.act + e * kAS + d] = act;
-                    }
-                }
-                a.logp[env] = lp;
-            }
+            a.val[env] = outs[e * OS + A];
+            if (!a.tail) sample_row(a, A, gls, env, outs + e * OS, lds + L.q.act + e * kAS);
         }
     }
     if (a.tail) return true;
-    if (blockIdx.x == 0 && tid >= 64 && tid < 64 + A) a.logstd[tid - 64] = log_f(exp_f(gls[tid - 64]));
+    logstd_write(a.logstd, gls, A, tid);
     wg_sync_lds(); // the actions; from here U is c_net's
     return false;
 }
@@ -193,112 +160,19 @@ GX_D void q_probe_front(float* lds, const Lds& L, const QArgs& q, const float* o
 // ---------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------
-// the values of gxu_status and gxp_status
-constexpr int kOk = 0, kErrArg = 1, kErrUnsupported = 2, kErrHip = 4;
-// the library's `fail`: records the message as the calling thread's last error and returns the status
-template <class Status>
-using FailFn = Status (*)(Status, const std::string&);
-
-constexpr size_t kLdsMax = 160 * 1024;
-
-bool width_ok(int H) { return H == 64 || H == 128 || H == 192 || H == 256; }
-bool shape_ok(int D, int A) { return D >= 1 && A >= 2 && A <= kMaxA && !(A & 1); }
-
-// the four gx?_*_floats entry points: -1 if unsupported
-int64_t params_floats(int D, int A, int H) { return (shape_ok(D, A) && width_ok(H)) ? net_floats(D, A, H) + net_floats(D, 1, H) + A : -1; }
+// the gx?_q_floats and gx?_probe_work_floats entry points: -1 if unsupported
 int64_t q_floats(int D, int A, int HC) { return (shape_ok(D, A) && width_ok(HC)) ? net_floats(D + A, 1, HC) : -1; }
-int64_t work_floats(int D, int A, int H, int HC)
-{
-    return (shape_ok(D, A) && width_ok(H) && width_ok(HC)) ? 2 * wt_floats(D, H) + wt_floats(D, HC) : -1;
-}
 int64_t probe_work_floats(int D, int A, int HC) { return (shape_ok(D, A) && width_ok(HC)) ? wt_floats(D, HC) : -1; }
 
 size_t step_lds_bytes(int D, int A, int H, int HC) { return sizeof(float) * (size_t)lds_layout(D, A, H, HC).total; }
 size_t probe_lds_bytes(int D, int A, int HC) { return sizeof(float) * (size_t)probe_lds_layout(D, A, HC).total; }
-
-template <class Status>
-Status check_shape(FailFn<Status> fail, const char* who, int D, int A, int H, int HC, bool probe)
-{
-    if (D < 1 || A < 1) return fail(Status(kErrArg), std::string(who) + ": D and A must be >= 1");
-    if (!width_ok(H) || !width_ok(HC))
-        return fail(Status(kErrUnsupported), std::string(who) + ": hidden width not in {64, 128, 192, 256}");
-    if (!shape_ok(D, A)) return fail(Status(kErrUnsupported), std::string(who) + ": needs an even action width <= 16");
-    if (D > 65536 || (probe ? probe_lds_bytes(D, A, HC) : step_lds_bytes(D, A, H, HC)) > kLdsMax)
-        return fail(Status(kErrUnsupported), std::string(who) + ": D too wide for the LDS tile");
-    return Status(kOk);
-}
-
-template <class Status>
-Status raise_lds(FailFn<Status> fail, const char* who, const void* kernel, size_t lds)
-{
-    if (lds > 64 * 1024) { // more dynamic LDS than the default cap: raise it for this kernel (on the current device)
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return fail(Status(kErrHip), std::string(who) + ": hipFuncSetAttribute failed");
-    }
-    return Status(kOk);
-}
-
-// Kernel dispatch.  K names a library's kernels: K::get<H, HC>() is the address of the instance (a probe kernel has no H
-// and ignores it).
-template <class K, int H>
-const void* q_kernel_hc(int HC)
-{
-    switch (HC) {
-    case 64: return K::template get<H, 64>();
-    case 128: return K::template get<H, 128>();
-    case 192: return K::template get<H, 192>();
-    default: return K::template get<H, 256>();
-    }
-}
-template <class K>
-const void* q_kernel_for(int H, int HC)
-{
-    switch (H) {
-    case 64: return q_kernel_hc<K, 64>(HC);
-    case 128: return q_kernel_hc<K, 128>(HC);
-    case 192: return q_kernel_hc<K, 192>(HC);
-    default: return q_kernel_hc<K, 256>(HC);
-    }
-}
-
-// `last` = hipGetLastError() after a <<< >>> launch or the result of hipLaunchKernel
-template <class Status>
-Status q_launched(FailFn<Status> fail, const char* who, hipError_t last)
-{
-    return last == hipSuccess ? Status(kOk) : fail(Status(kErrHip), std::string(who) + " launch failed: " + hipGetErrorString(last));
-}
-
-// one workgroup per 16 rows
-template <class Status, class Args>
-Status q_launch(FailFn<Status> fail, const char* who, const void* kernel, int n, Args& a, size_t lds, void* stream)
-{
-    void* kargs[] = {&a};
-    return q_launched(fail, who, hipLaunchKernel(kernel, dim3((unsigned)((n + kEnv - 1) / kEnv)), dim3(kThreads), kargs, lds,
-                                                  (hipStream_t)stream));
-}
-
-// the transposed hidden layers of `first` = 0: the three networks, 2: c_net alone, into d_work (n floats)
-template <class Status>
-Status q_transpose(FailFn<Status> fail, const char* who, long long n, const float* d_params, const float* d_c_params, float* d_work,
-                   int D, int A, int H, int HC, int first, void* stream)
-{
-    const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(usl_transpose_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_params, d_c_params, d_work, D, A,
-                       H, HC, first);
-    return q_launched(fail, who, hipGetLastError());
-}
 
 // gx?_prepare; StepK names the library's step kernels
 template <class StepK, class Status>
 Status q_prepare(FailFn<Status> fail, const char* who, int D, int A, int hidden, int c_hidden, const float* d_params,
                  const float* d_c_params, float* d_work, void* stream)
 {
-    if (!d_params || !d_c_params || !d_work) return fail(Status(kErrArg), std::string(who) + ": null pointer");
-    Status st = check_shape(fail, who, D, A, hidden, c_hidden, false);
-    if (st != Status(kOk)) return st;
-    st = raise_lds(fail, who, q_kernel_for<StepK>(hidden, c_hidden), step_lds_bytes(D, A, hidden, c_hidden));
-    if (st != Status(kOk)) return st;
-    return q_transpose(fail, who, work_floats(D, A, hidden, c_hidden), d_params, d_c_params, d_work, D, A, hidden, c_hidden, 0, stream);
+    return prepare<StepK>(fail, who, kRowD, step_lds_bytes, D, A, hidden, c_hidden, D + A, d_params, d_c_params, d_work, stream);
 }
 
 // the probe's own transpose of c_net into its scratch
@@ -306,7 +180,7 @@ template <class Status>
 Status q_probe_transpose(FailFn<Status> fail, const char* who, int D, int A, int c_hidden, const float* d_c_params, float* d_work,
                          void* stream)
 {
-    return q_transpose(fail, who, wt_floats(D, c_hidden), d_c_params, d_c_params, d_work, D, A, c_hidden, c_hidden, 2, stream);
+    return transpose(fail, who, wt_floats(D, c_hidden), d_c_params, d_c_params, d_work, D, A, c_hidden, c_hidden, D + A, 2, stream);
 }
 
 // a probe entry point after its own checks: the shape, the kernel's LDS, c_net's transpose, the launch over n rows
@@ -314,13 +188,13 @@ template <class ProbeK, class Status, class Args>
 Status q_probe_run(FailFn<Status> fail, const char* who, int n, int D, int A, int c_hidden, const float* d_c_params, float* d_work,
                    Args& a, void* stream)
 {
-    Status st = check_shape(fail, who, D, A, 64, c_hidden, true);
+    Status st = check_shape(fail, who, kRowD, [](int d, int a, int, int hc) { return probe_lds_bytes(d, a, hc); }, D, A, 64, c_hidden);
     if (st != Status(kOk) || n == 0) return st;
     const void* kernel = q_kernel_hc<ProbeK, 0>(c_hidden);
     const size_t lds = probe_lds_bytes(D, A, c_hidden);
     st = raise_lds(fail, who, kernel, lds);
     if (st == Status(kOk)) st = q_probe_transpose(fail, who, D, A, c_hidden, d_c_params, d_work, stream);
-    return st == Status(kOk) ? q_launch(fail, who, kernel, n, a, lds, stream) : st;
+    return st == Status(kOk) ? q_launch(fail, who, kernel, n, kThreads, a, lds, stream) : st;
 }
 
 // QArgs without the iteration's own niter and eta (USL sets them)
@@ -333,53 +207,24 @@ QArgs q_args(int D, int A, bool correct, float delta, float gscale, const float*
     return q;
 }
 
-// The checks gx?_policy_step makes before it launches.  own_range(g): the library's own range checks, named by the tail
-// `own_text` of the message; own_ptrs(g, tail): its own pointers are there.
+// The checks gx?_policy_step makes before it launches (gx_step.h:check_common with c_net's and the corrected action's
+// pointers).  own_range(g): the library's own range checks, named by the tail `own_text` of the message;
+// own_ptrs(g, tail): its own pointers are there.
 template <class Status, class G, class OwnRange, class OwnPtrs>
 Status q_check_common(FailFn<Status> fail, const char* who, const G* g, OwnRange own_range, const char* own_text, OwnPtrs own_ptrs)
 {
-    const std::string w(who);
-    if (!g) return fail(Status(kErrArg), w + ": null argument struct");
-    if (g->struct_size != sizeof(G)) return fail(Status(kErrArg), w + ": struct_size mismatch");
-    if (g->N < 0 || g->T < 1 || g->t < 0 || g->t > g->T || g->env_offset < 0 || !own_range(*g))
-        return fail(Status(kErrArg), w + ": N must be >= 0, T >= 1, t in [0, T], env_offset >= 0" + own_text);
-    const Status st = check_shape(fail, who, g->D, g->A, g->hidden, g->c_hidden, false);
-    if (st != Status(kOk)) return st;
-    const bool tail = g->t == g->T, prologue = g->t > 0;
-    if (!g->d_params || !g->d_c_params || !g->d_work || !own_ptrs(*g, tail)) return fail(Status(kErrArg), w + ": null pointer");
-    if (prologue ? (!g->d_obs_rd || !g->d_rew_in || !g->d_cost_in || !g->d_done_in || !g->d_rew || !g->d_cost || !g->d_done)
-                 : !g->d_obs0)
-        return fail(Status(kErrArg), w + ": null pointer");
-    if (tail ? (!g->d_obs_last || !g->d_val_last)
-             : (!g->d_obs || !g->d_act || !g->d_act_safe || !g->d_mu || !g->d_logp || !g->d_val || !g->d_qc || !g->d_logstd))
-        return fail(Status(kErrArg), w + ": null pointer");
-    return Status(kOk);
+    return check_common(fail, who, g, kRowD, step_lds_bytes, &G::D, &G::c_hidden, &G::d_c_params, own_range, own_text,
+                        [&](const G& s, bool tail) { return (tail || (s.d_act_safe && s.d_qc)) && own_ptrs(s, tail); });
 }
 
 // the shared fields of a checked gx?_step_args; returns the offset of row block t in a [T][N] array (0 in the tail)
 template <class G>
 size_t q_fill_common(const G& g, QStepCommon& c)
 {
-    const size_t N = (size_t)g.N, D = (size_t)g.D, A = (size_t)g.A;
-    c.N = g.N; c.env_offset = g.env_offset;
-    c.tail = g.t == g.T; c.prologue = g.t > 0;
-    c.seed0 = g.seed[0]; c.seed1 = g.seed[1]; c.tnoise = g.step0 + (uint32_t)g.t;
+    const size_t tn = fill_common(g, g.D, c);
     c.q = q_args(g.D, g.A, g.correct != 0, g.delta, g.grad_scale, g.d_c_params, g.d_work + 2 * wt_floats(g.D, g.hidden));
-    c.params = g.d_params; c.wt = g.d_work;
-    c.obs_rd = c.prologue ? g.d_obs_rd : g.d_obs0;
-    c.rew_in = g.d_rew_in; c.cost_in = g.d_cost_in; c.done_in = g.d_done_in;
-    const size_t tp = c.prologue ? (size_t)(g.t - 1) * N : 0;
-    c.rew_p = c.prologue ? g.d_rew + tp : nullptr; c.cost_p = c.prologue ? g.d_cost + tp : nullptr;
-    c.done_p = c.prologue ? g.d_done + tp : nullptr;
-    if (c.tail) {
-        c.obs = g.d_obs_last; c.val = g.d_val_last;
-        c.act = c.act_safe = c.mu = c.logp = c.qc = c.logstd = nullptr;
-        return 0;
-    }
-    const size_t tn = (size_t)g.t * N;
-    c.obs = g.d_obs + tn * D; c.act = g.d_act + tn * A; c.act_safe = g.d_act_safe + tn * A;
-    c.mu = g.d_mu + tn * A; c.logp = g.d_logp + tn; c.val = g.d_val + tn;
-    c.qc = g.d_qc + tn; c.logstd = g.d_logstd;
+    c.act_safe = c.tail ? nullptr : g.d_act_safe + tn * (size_t)g.A;
+    c.qc = c.tail ? nullptr : g.d_qc + tn;
     return tn;
 }
 

@@ -22,8 +22,8 @@
 //
 // Here: the iteration's per-row logic (the two tests, the update, the `live` vote), the two kernels and the C entry
 // points.  The pass over c_net is gx_qcritic.h:q_pass; the step kernel's front end (ac.step up to the sampled action),
-// the probe kernel's, the LDS layouts and the host side's checks, dispatch and launches are gx_qstep.h's, shared with
-// gx_lpg.hip.
+// the probe kernel's and the LDS layouts are gx_qstep.h's, shared with gx_lpg.hip; the sample / log-prob block, the MFMA
+// chain and the host side's checks, dispatch and launches are gx_step.h's, shared with every step library.
 #include "../../include/guardx_usl.h"
 #include "gx_qstep.h"
 
@@ -198,7 +198,7 @@ extern "C" gxu_status gxu_policy_step(const gxu_step_args* g, void* stream)
     const size_t tn = q_fill_common(*g, a.c);
     a.c.q.niter = g->niter; a.c.q.eta = g->eta;
     a.iters = a.c.tail ? nullptr : g->d_iters + tn;
-    return q_launch(fail, "gxu_policy_step", q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, a,
+    return q_launch(fail, "gxu_policy_step", q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, kThreads, a,
                     step_lds_bytes(g->D, g->A, g->hidden, g->c_hidden), stream);
 }
 

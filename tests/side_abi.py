@@ -1,6 +1,6 @@
 """The C header of a side library (include/guardx_<key>.h, prefix gx?_) parsed into ctypes prototypes, and the
-comparison of the library's binding (guardx_amd/_<key>_native.py) with it: shared by the host suites of the usl and the
-lpg library."""
+comparison of the library's binding (guardx_amd/_<key>_native.py) with it: shared by the host suites of the statewise,
+the safelayer, the usl and the lpg library."""
 import ctypes as C
 import os
 import re
@@ -35,10 +35,10 @@ def prototypes(key, prefix, step_args):
     return protos
 
 
-def assert_binding_matches_the_header(key, prefix, n, step_args):
-    """the 9 prototypes, the fields of gx?_step_args in order and the status values of binding module `n`"""
+def assert_binding_matches_the_header(key, prefix, n, step_args, count):
+    """the `count` prototypes, the fields of gx?_step_args in order and the status values of binding module `n`"""
     protos = prototypes(key, prefix, step_args)
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 9
+    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == count
     for name, (res, args) in protos.items():
         assert n.SYMBOLS[name] == (res, args), name
     body = re.search(r"typedef struct %s_step_args \{(.*?)\} %s_step_args;" % (prefix, prefix), header(key), flags=re.S).group(1)

@@ -76,9 +76,13 @@ def _assert_warmup_equal(g, w, what):
     np.testing.assert_array_equal(bits(g['act_safe']), bits(g['act']), err_msg=f"{what} act_safe")
 
 
-@pytest.mark.parametrize("N", [17, 2000])
-@pytest.mark.parametrize("h,hg", [(64, 64), (256, 128)])
-@pytest.mark.parametrize("robot", ["point", "swimmer", "ant"])
+# every robot at both width pairs with a ragged last workgroup and many workgroups; the lone row and the exactly full
+# workgroup once
+WARMUP_CASES = [(robot, h, hg, N) for robot in ("point", "swimmer", "ant") for h, hg in ((64, 64), (256, 128))
+                for N in (17, 2000)] + [("point", 64, 64, 1), ("point", 64, 64, 16)]
+
+
+@pytest.mark.parametrize("robot,h,hg,N", WARMUP_CASES)
 def test_warmup_is_bit_equal_to_rollout_policy(robot, h, hg, N):
     """correct=False: the actor, v, the noise and the env give rollout_policy's bits (step-wise form on a twin engine),
     over resets inside the call (num_steps 5 < T) and a second call that continues the noise counter; and the engine is

@@ -31,7 +31,7 @@ def test_lpg_source_hash_covers_its_sources_and_the_shared_header():
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
     have = {norm(h) for h in libs["lpg"].headers}
     incs = set()
-    for f in ("gx_lpg.hip", "gx_qstep.h", "gx_qcritic.h"):
+    for f in ("gx_lpg.hip", "gx_qstep.h", "gx_qcritic.h", "gx_step.h"):
         incs |= {norm(i) for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())}
     assert incs <= have and norm("gx_qstep.h") in incs
     assert {norm("gx_qstep.h"), norm("gx_qcritic.h"), norm("gx_device.h"), norm("../../include/guardx_lpg.h")} <= have
@@ -42,13 +42,14 @@ def test_lpg_source_hash_covers_its_sources_and_the_shared_header():
 
 
 def test_the_older_build_ids_do_not_cover_the_shared_header():
-    """critic, statewise and safelayer hash exactly the file lists they hashed before gx_qcritic.h existed (their source,
-    gx_device.h, gx_policy.h and their own header), and libguardx_hip.so's id is still the recorded one"""
+    """critic hashes exactly the file list it hashed before gx_qcritic.h existed (its source, gx_device.h, gx_policy.h and
+    its own header), statewise and safelayer that list and gx_step.h, and libguardx_hip.so's id is still the recorded one"""
     from guardx_amd import build
     libs = build.LIBRARIES
-    for key, src in (("critic", "gx_critic.hip"), ("statewise", "gx_statewise.hip"), ("safelayer", "gx_safelayer.hip")):
+    for key, src, step in (("critic", "gx_critic.hip", []), ("statewise", "gx_statewise.hip", ["gx_step.h"]),
+                           ("safelayer", "gx_safelayer.hip", ["gx_step.h"])):
         lib = libs[key]
-        names = [src, "gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_%s.h" % key)]
+        names = [src, "gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_%s.h" % key)] + step
         assert sorted(set(lib.sources) | set(lib.headers)) == sorted(names)
         assert not any("qcritic" in h or "lpg" in h for h in lib.headers)
         h = hashlib.sha256()
@@ -60,6 +61,7 @@ def test_the_older_build_ids_do_not_cover_the_shared_header():
         h.update(repr(build.FLAGS).encode())
         assert lib.source_hash() == h.hexdigest()[:24], key
     assert not any("qcritic" in h or "lpg" in h for h in build.HEADERS + build.SOURCES)
+    assert "gx_step.h" not in build.HEADERS + build.SOURCES
     recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
     assert build.source_hash() == recorded
     ids = {lib.source_hash() for lib in libs.values()} | {build.source_hash()}
@@ -73,7 +75,7 @@ def _prototypes():
 
 def test_binding_matches_the_header():
     from guardx_amd import _lpg_native as n
-    side_abi.assert_binding_matches_the_header("lpg", "gxp", n, n.GxpStepArgs)
+    side_abi.assert_binding_matches_the_header("lpg", "gxp", n, n.GxpStepArgs, 9)
 
 
 @pytest.fixture(scope="module")

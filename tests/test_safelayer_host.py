@@ -12,6 +12,7 @@ from oracle import policy64
 from oracle.trpo_buffer_np import TRPOBufferNP
 from helpers import task_config
 import safelayer64
+import side_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -94,11 +95,12 @@ def test_safelayer_source_hash_covers_its_sources():
     from guardx_amd import build
     libs = build.LIBRARIES
     assert libs["safelayer"].sources == ["gx_safelayer.hip"]
-    incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_safelayer.hip")).read())
+    incs = [i for f in ("gx_safelayer.hip", "gx_step.h")
+            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
     have = {norm(h) for h in libs["safelayer"].headers}
     assert {norm(i) for i in incs} <= have
-    assert norm("gx_device.h") in have                                # gx_policy.h's own include
+    assert "gx_step.h" in incs and norm("gx_device.h") in have        # gx_policy.h's own include
     # its own library: nothing of it is hashed into the three older ones, whose identities stand
     older = set(build.SOURCES) | set(libs["critic"].sources) | set(libs["statewise"].sources)
     assert not (set(libs["safelayer"].sources) & older)
@@ -113,69 +115,25 @@ def test_safelayer_hash_changes_with_a_source(monkeypatch, tmp_path):
     from guardx_amd import build
     libs = build.LIBRARIES
     before = libs["safelayer"].source_hash()
-    for n in ["gx_safelayer.hip", "gx_device.h", "gx_policy.h"]:
+    for n in ["gx_safelayer.hip", "gx_device.h", "gx_policy.h", "gx_step.h"]:
         (tmp_path / n).write_bytes(open(os.path.join(build.CSRC, n), "rb").read())
     inc = tmp_path.parent / "include_sl"
     inc.mkdir(exist_ok=True)
     hdr = open(os.path.join(ROOT, "include", "guardx_safelayer.h"), "rb").read()
     (inc / "guardx_safelayer.h").write_bytes(hdr + b"\n")
     monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    monkeypatch.setattr(libs["safelayer"], "headers", ["gx_device.h", "gx_policy.h", os.path.join("..", "include_sl", "guardx_safelayer.h")])
+    monkeypatch.setattr(libs["safelayer"], "headers", ["gx_device.h", "gx_policy.h", "gx_step.h", os.path.join("..", "include_sl", "guardx_safelayer.h")])
     assert libs["safelayer"].source_hash() != before                    # the header is part of the identity
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "guardx_safelayer.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-_CTYPES = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "gxl_status": C.c_int, "float": C.c_float,
-           "const char*": C.c_char_p, "void*": C.c_void_p, "const float*": C.c_void_p, "float*": C.c_void_p}
-
-
-def _ctype(decl):
-    from guardx_amd._safelayer_native import GxlStepArgs
-    t = re.sub(r"\s+", " ", decl.strip())
-    t = re.sub(r"\s*\*\s*", "* ", t).strip()
-    t = re.sub(r"\s+[A-Za-z_][A-Za-z_0-9]*$", "", t) if not t.endswith("*") and " " in t else t
-    t = t.strip()
-    if t == "const gxl_step_args*":
-        return C.POINTER(GxlStepArgs)
-    return _CTYPES[t]
-
-
 def _prototypes():
-    protos = {}
-    for ret, name, args in re.findall(r"([A-Za-z_0-9 ]+?\*?)\s*\b(gxl_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", _header()):
-        args = args.strip()
-        argt = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
-        protos[name] = (_ctype(ret.strip() + " x") if not ret.strip().endswith("*") else _ctype(ret), argt)
-    return protos
+    from guardx_amd._safelayer_native import GxlStepArgs
+    return side_abi.prototypes("safelayer", "gxl", GxlStepArgs)
 
 
 def test_binding_matches_the_header():
     from guardx_amd import _safelayer_native as n
-    protos = _prototypes()
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 8
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    body = re.search(r"typedef struct gxl_step_args \{(.*?)\} gxl_step_args;", _header(), flags=re.S).group(1)
-    fields = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        m = re.match(r"(const float\*|float\*|uint32_t|int32_t|float)\s+(.*)", stmt)
-        base = {"const float*": C.c_void_p, "float*": C.c_void_p, "uint32_t": C.c_uint32, "int32_t": C.c_int32,
-                "float": C.c_float}[m.group(1)]
-        for nm in m.group(2).split(","):
-            nm = nm.strip()
-            arr = re.match(r"(\w+)\[(\d+)\]", nm)
-            fields.append((arr.group(1), base * int(arr.group(2))) if arr else (nm, base))
-    assert [(f[0], f[1]) for f in n.GxlStepArgs._fields_] == fields
-    st = dict(re.findall(r"(GXL_[A-Z_]+) = (\d+)", _header()))
-    assert {k: int(v) for k, v in st.items()} == {"GXL_OK": n.GXL_OK, "GXL_ERR_ARG": n.GXL_ERR_ARG,
-                                                 "GXL_ERR_UNSUPPORTED": n.GXL_ERR_UNSUPPORTED, "GXL_ERR_HIP": n.GXL_ERR_HIP}
+    side_abi.assert_binding_matches_the_header("safelayer", "gxl", n, n.GxlStepArgs, 8)
 
 
 @pytest.fixture(scope="module")
@@ -206,6 +164,21 @@ def test_a_foreign_build_id_is_refused(sl_lib, monkeypatch):
     monkeypatch.setattr(libs["safelayer"], "needs_build", lambda: False)
     with pytest.raises(ImportError, match="built from other sources"):
         n.load()
+
+
+def test_no_scratch_in_the_device_code(tmp_path):
+    """hipcc --offload-arch=gfx950 compiles every kernel of the library (16 step kernels, the probe kernel, the transpose)
+    without scratch memory and within the 168 registers that 12 waves per workgroup (3 on a SIMD, 512 / 3 rounded down) leave a lane"""
+    import subprocess
+    from guardx_amd import build
+    asm = tmp_path / "gx_safelayer.s"
+    subprocess.check_call([os.environ.get("HIPCC", "hipcc")] + build.FLAGS + ["--cuda-device-only", "-S", "-o", str(asm),
+                                                                             os.path.join(build.CSRC, "gx_safelayer.hip")])
+    text = asm.read_text()
+    scratch = [int(v) for v in re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", text)]
+    vgpr = [int(v) for v in re.findall(r"\.amdhsa_next_free_vgpr\s+(\d+)", text)]
+    print("safelayer kernels:", len(scratch), "max vgpr", max(vgpr))
+    assert len(scratch) == 18 and max(scratch) == 0 and max(vgpr) <= 168
 
 
 def test_sizes_and_bad_arguments_are_errors_not_crashes(sl_lib):

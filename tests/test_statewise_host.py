@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.trpo_buffer_np import TRPOBufferNP, discount_cumsum
+import side_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -68,11 +69,12 @@ def test_statewise_source_hash_covers_its_sources():
     from guardx_amd import build
     libs = build.LIBRARIES
     assert libs["statewise"].sources == ["gx_statewise.hip"]
-    incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_statewise.hip")).read())
+    incs = [i for f in ("gx_statewise.hip", "gx_step.h")
+            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
     have = {norm(h) for h in libs["statewise"].headers}
     assert {norm(i) for i in incs} <= have
-    assert norm("gx_device.h") in have                                # gx_policy.h's own include
+    assert "gx_step.h" in incs and norm("gx_device.h") in have        # gx_policy.h's own include
     # its own library: nothing of it is hashed into the main library or the critic's, whose identities stand
     assert not (set(libs["statewise"].sources) & (set(build.SOURCES) | set(libs["critic"].sources)))
     assert all("statewise" not in h for h in build.HEADERS + libs["critic"].headers)
@@ -86,69 +88,25 @@ def test_statewise_hash_changes_with_a_source(monkeypatch, tmp_path):
     from guardx_amd import build
     libs = build.LIBRARIES
     before = libs["statewise"].source_hash()
-    for n in ["gx_statewise.hip", "gx_device.h", "gx_policy.h"]:
+    for n in ["gx_statewise.hip", "gx_device.h", "gx_policy.h", "gx_step.h"]:
         (tmp_path / n).write_bytes(open(os.path.join(build.CSRC, n), "rb").read())
     inc = tmp_path.parent / "include_sw"
     inc.mkdir(exist_ok=True)
     hdr = open(os.path.join(ROOT, "include", "guardx_statewise.h"), "rb").read()
     (inc / "guardx_statewise.h").write_bytes(hdr + b"\n")
     monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    monkeypatch.setattr(libs["statewise"], "headers", ["gx_device.h", "gx_policy.h", os.path.join("..", "include_sw", "guardx_statewise.h")])
+    monkeypatch.setattr(libs["statewise"], "headers", ["gx_device.h", "gx_policy.h", "gx_step.h", os.path.join("..", "include_sw", "guardx_statewise.h")])
     assert libs["statewise"].source_hash() != before                    # the header is part of the identity
 
 
-def _header():
-    text = open(os.path.join(ROOT, "include", "guardx_statewise.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-_CTYPES = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "gxs_status": C.c_int,
-           "const char*": C.c_char_p, "void*": C.c_void_p, "const float*": C.c_void_p, "float*": C.c_void_p}
-
-
-def _ctype(decl):
-    from guardx_amd._statewise_native import GxsStepArgs
-    t = re.sub(r"\s+", " ", decl.strip())
-    t = re.sub(r"\s*\*\s*", "* ", t).strip()
-    t = re.sub(r"\s+[A-Za-z_][A-Za-z_0-9]*$", "", t) if not t.endswith("*") and " " in t else t
-    t = t.strip()
-    if t == "const gxs_step_args*":
-        return C.POINTER(GxsStepArgs)
-    return _CTYPES[t]
-
-
 def _prototypes():
-    protos = {}
-    for ret, name, args in re.findall(r"([A-Za-z_0-9 ]+?\*?)\s*\b(gxs_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", _header()):
-        args = args.strip()
-        argt = [] if args in ("", "void") else [_ctype(a) for a in args.split(",")]
-        protos[name] = (_ctype(ret.strip() + " x") if not ret.strip().endswith("*") else _ctype(ret), argt)
-    return protos
+    from guardx_amd._statewise_native import GxsStepArgs
+    return side_abi.prototypes("statewise", "gxs", GxsStepArgs)
 
 
 def test_binding_matches_the_header():
     from guardx_amd import _statewise_native as n
-    protos = _prototypes()
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 7
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    # the argument struct, field for field
-    body = re.search(r"typedef struct gxs_step_args \{(.*?)\} gxs_step_args;", _header(), flags=re.S).group(1)
-    fields = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        m = re.match(r"(const float\*|float\*|uint32_t|int32_t)\s+(.*)", stmt)
-        base = {"const float*": C.c_void_p, "float*": C.c_void_p, "uint32_t": C.c_uint32, "int32_t": C.c_int32}[m.group(1)]
-        for nm in m.group(2).split(","):
-            nm = nm.strip()
-            arr = re.match(r"(\w+)\[(\d+)\]", nm)
-            fields.append((arr.group(1), base * int(arr.group(2))) if arr else (nm, base))
-    assert [(f[0], f[1]) for f in n.GxsStepArgs._fields_] == fields
-    st = dict(re.findall(r"(GXS_[A-Z_]+) = (\d+)", _header()))
-    assert {k: int(v) for k, v in st.items()} == {"GXS_OK": n.GXS_OK, "GXS_ERR_ARG": n.GXS_ERR_ARG,
-                                                 "GXS_ERR_UNSUPPORTED": n.GXS_ERR_UNSUPPORTED, "GXS_ERR_HIP": n.GXS_ERR_HIP}
+    side_abi.assert_binding_matches_the_header("statewise", "gxs", n, n.GxsStepArgs, 7)
 
 
 @pytest.fixture(scope="module")
@@ -169,6 +127,21 @@ def test_export_list_equals_the_header(sw_lib):
     for other in (_native.LIB_PATH, _critic_native.LIB_PATH):
         lib = C.CDLL(other)
         assert not any(hasattr(lib, s) for s in n.SYMBOLS)
+
+
+def test_no_scratch_in_the_device_code(tmp_path):
+    """hipcc --offload-arch=gfx950 compiles every kernel of the library (16 step kernels, the probe kernel, the transpose)
+    without scratch memory and within the 256 registers that 6 waves per workgroup (at most 2 on a SIMD) leave a lane"""
+    import subprocess
+    from guardx_amd import build
+    asm = tmp_path / "gx_statewise.s"
+    subprocess.check_call([os.environ.get("HIPCC", "hipcc")] + build.FLAGS + ["--cuda-device-only", "-S", "-o", str(asm),
+                                                                             os.path.join(build.CSRC, "gx_statewise.hip")])
+    text = asm.read_text()
+    scratch = [int(v) for v in re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", text)]
+    vgpr = [int(v) for v in re.findall(r"\.amdhsa_next_free_vgpr\s+(\d+)", text)]
+    print("statewise kernels:", len(scratch), "max vgpr", max(vgpr))
+    assert len(scratch) == 18 and max(scratch) == 0 and max(vgpr) <= 256
 
 
 def test_sizes_and_bad_arguments_are_errors_not_crashes(sw_lib):

@@ -59,7 +59,7 @@ def test_usl_source_hash_covers_its_sources_and_leaves_the_older_libraries_alone
     from guardx_amd import build
     libs = build.LIBRARIES
     assert libs["usl"].sources == ["gx_usl.hip"]
-    incs = [i for f in ("gx_usl.hip", "gx_qstep.h", "gx_qcritic.h")
+    incs = [i for f in ("gx_usl.hip", "gx_qstep.h", "gx_qcritic.h", "gx_step.h")
             for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
     norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
     have = {norm(h) for h in libs["usl"].headers}
@@ -84,7 +84,7 @@ def _prototypes():
 
 def test_binding_matches_the_header():
     from guardx_amd import _usl_native as n
-    side_abi.assert_binding_matches_the_header("usl", "gxu", n, n.GxuStepArgs)
+    side_abi.assert_binding_matches_the_header("usl", "gxu", n, n.GxuStepArgs, 9)
 
 
 @pytest.fixture(scope="module")
