@@ -1,5 +1,5 @@
 """Build libguardx_hip.so and the side libraries of LIBRARIES (libguardx_critic.so, libguardx_statewise.so,
-libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so) for gfx950 in-tree with hipcc.
+libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so, libguardx_episode.so) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -63,11 +63,12 @@ def _extra(src):
 BUILD_ID_FILE = os.path.join(LIB_DIR, "BUILD_ID")
 LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 
-# The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer, the USL and the LPG policy step.
+# The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer, the USL, the LPG and the
+# one-episode policy step.
 # Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
 # libguardx_hip.so -- and the profiles taken on that build -- alone.
 _SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
-# what the four step libraries share (sizes, the transpose kernel, the MFMA chain, the sample / log-prob block, the host
+# what the five step libraries share (sizes, the transpose kernel, the MFMA chain, the sample / log-prob block, the host
 # side's checks, dispatch and launches): not the critic library's, whose build id does not cover it
 _STEP_HEADERS = _SIDE_HEADERS + ["gx_step.h"]
 # c_net's device code and the front end of its step and probe kernels, shared by the two learners that correct the action
@@ -114,6 +115,7 @@ LIBRARIES = {lib.key: lib for lib in (
     SideLibrary("safelayer", "GXL_BUILD_ID", ["gx_safelayer.hip"], _STEP_HEADERS),
     SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _Q_HEADERS),
     SideLibrary("lpg", "GXP_BUILD_ID", ["gx_lpg.hip"], _Q_HEADERS),
+    SideLibrary("episode", "GXE_BUILD_ID", ["gx_episode.hip"], _STEP_HEADERS),
 )}
 
 
@@ -184,7 +186,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All six libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All seven libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)

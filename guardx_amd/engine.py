@@ -336,6 +336,7 @@ class Engine:
         self._safelayer = None       # rollout_safelayer's prev_c / step counter (guardx_amd/safelayer.py), made on first use
         self._usl = None             # rollout_usl's step counter and slab (guardx_amd/usl.py), made on first use
         self._lpg = None             # rollout_lpg's q_init / step counter and slab (guardx_amd/lpg.py), made on first use
+        self._episode = None         # rollout_episode's first_done / sums / step counter (guardx_amd/episode.py), made on first use
         self._obs = None
         self._reward = None
         self._done = None
@@ -486,6 +487,8 @@ class Engine:
             self._statewise.reset()     # M = 0, first = 1 (scpo.py:637-639, 697-699)
         if self._safelayer is not None:
             self._safelayer.reset()     # prev_c = 0 (safelayer.py:507, 567)
+        if self._episode is not None:
+            self._episode.reset()       # first_done = ep_ret = ep_cost = ep_len = 0, the episode starts over
         if not check:
             self._obs = obs
             return obs
@@ -937,6 +940,25 @@ class Engine:
         step(), reset() and the other rollouts neither read nor change either."""
         from . import lpg as _lpg
         return _lpg.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, store_init, grad_scale, step_sign)
+
+    def rollout_episode(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
+        """T x (zero the NaN / Inf entries of obs -> ac.step -> env.step) on device, with NO reset_done: the collection
+        loop of the `*_one_episode` learners (trpo_one_episode/trpo.py:450-545, cpo_one_episode/cpo.py:619-708) whose
+        ac.step is the actor and v, or with cost_critic = pack_critic(ac.vc) the actor, v and vc.  `params` =
+        pack_actor_critic(ac).  A finished env keeps being stepped; per env the path keeps first_done (the 1-based index
+        of the first step with done, 0 = not finished), ep_ret / ep_cost (reward and cost summed up to and including that
+        step, float32, one add per step) and ep_len (the steps counted).  Two launches per control step
+        (guardx_amd/episode.py).
+        Returns a dict of time-major tensors: obs (T,N,D) [what the networks saw: non-finite entries are +0.0], act, mu
+        (T,N,A), logp, val, rew, cost, done (T,N), with cost_critic vc (T,N) and vc_last (N,), plus obs_last (N,D) [the
+        env's row as it is], val_last (N,) [0 for a row with a non-finite entry, like vc_last], logstd (A,), copies of
+        the state after the call first_done, ep_len (int32), ep_ret, ep_cost (N,) and t0, the steps the episode had
+        made before the call.  The state persists across calls (an episode may be collected in several, t0 advancing by
+        T); reset() clears it; step() and the other rollouts neither read nor write it.  The noise counter is this
+        path's own (0 at construction, + T per call, not reset by reset()).
+        rollout_buffer.episode_rollout_batch turns the result of a whole episode into the learner's batch."""
+        from . import episode as _ep
+        return _ep.rollout(self, params, T, obs0, noise_seed, cost_critic)
 
     def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of

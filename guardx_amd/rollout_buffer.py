@@ -281,3 +281,118 @@ def lpg_rollout_batch(out, gamma=0.99, lam=0.95):
     env, targetc[t] = cost[t] + gamma qc[t + 1] with qc of the UNCORRECTED action and 0 past the end of a path.  (`lam`
     here is GAE's lambda; out['lam'], the projection's multiplier, is not part of the batch.)"""
     return _q_target_batch(out, gamma, lam, "lpg_rollout_batch", "Engine.rollout_lpg")
+
+
+def _episode_lengths(first_done, T):
+    """L = first_done ? min(first_done, T) : T, int64 (N,)"""
+    fd = first_done.to(torch.int64)
+    return torch.where(fd > 0, fd.clamp(max=T), torch.full_like(fd, T))
+
+
+def _episode_channel_host(rew, val, last, L, finished, gamma, lam, scale):
+    """One channel of gxe_finish in torch, operation for operation (include/guardx_episode.h): (T, N) host tensors ->
+    (advantage (T, N) normalised over all T entries of an env, or centred only; returns-to-go (T, N)), 0 on [L, T)."""
+    T, N = rew.shape
+    f32, f64 = torch.float32, torch.float64
+    g32 = torch.tensor(gamma, dtype=f32)
+    dg = float(g32)
+    dgl = dg * float(torch.tensor(lam, dtype=f32))
+    boot = torch.where(finished, torch.zeros(N, dtype=f32), last.to(f32))
+    adv, ret = torch.zeros(T, N, dtype=f32), torch.zeros(T, N, dtype=f32)
+    a, r, v_next, s = torch.zeros(N, dtype=f64), boot.to(f64), boot.clone(), torch.zeros(N, dtype=f32)
+    for t in range(T - 1, -1, -1):
+        m = L > t                                   # the envs whose path holds step t
+        delta = (rew[t] + g32 * v_next) - val[t]
+        a = torch.where(m, delta.to(f64) + dgl * a, a)
+        r = torch.where(m, rew[t].to(f64) + dg * r, r)
+        adv[t] = torch.where(m, a.to(f32), adv[t])
+        ret[t] = torch.where(m, r.to(f32), ret[t])
+        s = torch.where(m, s + adv[t], s)
+        v_next = torch.where(m, val[t], v_next)
+    Tf = torch.tensor(float(T), dtype=f32)
+    mean = s / Tf
+    if not scale:
+        return torch.where(L > torch.arange(T).view(T, 1), adv - mean, adv), ret
+    q = torch.zeros(N, dtype=f32)
+    for t in range(T):
+        d = adv[t] - mean
+        q = q + d * d
+    # the square root through float64: torch's float32 sqrt on the CPU is not correctly rounded on every build, the
+    # device's is, and the float64 root of a float32 value rounds to the correctly rounded float32 root
+    sd = (q / Tf).to(f64).sqrt().to(f32)
+    return (adv - mean) / sd, ret
+
+
+def episode_rollout_batch(out, gamma=0.99, lam=0.95):
+    """An Engine.rollout_episode result covering a whole episode (out['t0'] == 0, else ValueError) as the batch the
+    one-episode buffer's get() returns after its finish_path (trpo_one_episode/trpo.py:67-132, cpo_one_episode/
+    cpo.py:72-156), first epoch.  Per env, with L = first_done or T: GAE-lambda and rewards-to-go over [0, L), closed with
+    val_last for the envs that never finished and with 0 for the others; adv normalised over ALL T entries of the env's
+    row, the zeros on [L, T) included (mpi_tools.py:81-86; no guard on a zero deviation); with out['vc'] the same on
+    cost / vc / vc_last, centred only.  Then the valid rows only, env-major, in the order x.view(N T, .)[valid] gives:
+    obs act ret adv logp mu logstd (+ cost_ret adc), each a view of the first n_valid rows of an (N T)-row tensor whose
+    other rows are left unwritten, and n_valid.  Device tensors: two launches (gxe_finish) and ONE .item(), the only
+    synchronisation.  Host tensors (a result moved to the CPU) go through the same recursion in torch, operation for
+    operation, so the two agree bit for bit.
+    (The reference never re-zeroes adv_buf / adc_buf between epochs: from its second epoch on the entries past
+    first_done hold the previous epoch's normalised values and leak into mean and deviation.  Here they are 0, which is
+    what its first epoch sees.)"""
+    keys = ('obs', 'act', 'mu', 'logp', 'rew', 'val', 'val_last', 'logstd', 'first_done', 't0')
+    _require(out, keys, "episode_rollout_batch", "Engine.rollout_episode")
+    if int(out['t0']) != 0:
+        raise ValueError(f"episode_rollout_batch needs the call that starts the episode (out['t0'] == 0), got t0 = {out['t0']}")
+    has_cost = 'vc' in out
+    if has_cost:
+        _require(out, ('cost', 'vc_last'), "episode_rollout_batch", "Engine.rollout_episode(..., cost_critic=...)")
+    T, N = out['rew'].shape
+    D, A = out['obs'].shape[-1], out['act'].shape[-1]
+    # gxe_finish is handed raw pointers: every tensor must have the shape the sizes above promise
+    shapes = dict(obs=(T, N, D), act=(T, N, A), mu=(T, N, A), logp=(T, N), val=(T, N), val_last=(N,), first_done=(N,),
+                  logstd=(A,))
+    if has_cost:
+        shapes.update(cost=(T, N), vc=(T, N), vc_last=(N,))
+    for k, want in shapes.items():
+        if tuple(out[k].shape) != want:
+            raise ValueError(f"episode_rollout_batch: out['{k}'] has shape {tuple(out[k].shape)}; expected {want} "
+                             f"(from out['rew'] {(T, N)}, out['obs'] and out['act'])")
+    f = lambda x: x.to(torch.float32).contiguous()   # noqa: E731
+    if not out['rew'].is_cuda:
+        L = _episode_lengths(out['first_done'], T)
+        finished = out['first_done'] > 0
+        valid = (torch.arange(T).view(1, T) < L.view(N, 1)).reshape(N * T)
+        pick = lambda x: _env_major(f(x)).reshape(N * T, *x.shape[2:])[valid]   # noqa: E731
+        adv, ret = _episode_channel_host(f(out['rew']), f(out['val']), out['val_last'], L, finished, gamma, lam, 1)
+        n_valid = int(L.sum())
+        batch = dict(obs=pick(out['obs']), act=pick(out['act']), ret=pick(ret), adv=pick(adv), logp=pick(out['logp']),
+                     mu=pick(out['mu']))
+        if has_cost:
+            adc, cost_ret = _episode_channel_host(f(out['cost']), f(out['vc']), out['vc_last'], L, finished, gamma, lam, 0)
+            batch.update(cost_ret=pick(cost_ret), adc=pick(adc))
+    else:
+        from . import _episode_native
+        lib = _episode_native.load()
+        dev = out['rew'].device
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
+        src = {k: f(out[k]) for k in ('obs', 'act', 'mu', 'logp', 'rew', 'val', 'val_last')}
+        cost = {k: f(out[k]) for k in ('cost', 'vc', 'vc_last')} if has_cost else {}
+        fd = out['first_done'].to(device=dev, dtype=torch.int32).contiguous()
+        batch = dict(obs=new(N * T, D), act=new(N * T, A), ret=new(N * T), adv=new(N * T), logp=new(N * T), mu=new(N * T, A))
+        if has_cost:
+            batch.update(cost_ret=new(N * T), adc=new(N * T))
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        work = new(int(lib.gxe_finish_work_floats(N, T)))
+        cp = lambda k: cost[k].data_ptr() if has_cost else None   # noqa: E731
+        bp = lambda k: batch[k].data_ptr() if has_cost else None   # noqa: E731
+        with torch.cuda.device(dev):
+            _episode_native.check(lib.gxe_finish(
+                N, T, D, A, float(gamma), float(lam), fd.data_ptr(), src['obs'].data_ptr(), src['act'].data_ptr(),
+                src['mu'].data_ptr(), src['logp'].data_ptr(), src['rew'].data_ptr(), src['val'].data_ptr(),
+                src['val_last'].data_ptr(), cp('cost'), cp('vc'), cp('vc_last'), work.data_ptr(), batch['obs'].data_ptr(),
+                batch['act'].data_ptr(), batch['mu'].data_ptr(), batch['logp'].data_ptr(), batch['ret'].data_ptr(),
+                batch['adv'].data_ptr(), bp('cost_ret'), bp('adc'), count.data_ptr(),
+                C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))))
+        n_valid = int(count.item())
+        batch = {k: v[:n_valid] for k, v in batch.items()}
+    batch['logstd'] = out['logstd'].reshape(1, A).expand(n_valid, A).contiguous()
+    batch['n_valid'] = n_valid
+    return batch
