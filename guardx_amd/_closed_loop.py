@@ -1,4 +1,5 @@
-"""What the closed-loop rollouts with a third network share (statewise.py, safelayer.py, usl.py, lpg.py): the sizes of
+"""What the closed-loop rollouts with a third network share (statewise.py, safelayer.py, usl.py, lpg.py; the
+one-episode form of the last three: Book, run_episode, tail_probe): the sizes of
 the packed networks, the checks of the inputs (for the two learners with a Q critic, usl.py and lpg.py, also those of
 their probes and the tensors their rollouts return), the common fields of a gx?_step_args, the loop itself -- per control step the
 path's policy-step launch and one `gx_step_slab` launch (env.step with the speculated reset_done, committed on the
@@ -9,6 +10,7 @@ import ctypes as C
 import torch
 
 from . import _native
+from ._sidelib import FirstDoneState
 from .critic import HIDDEN
 
 
@@ -124,9 +126,34 @@ def flatten(lin, device):
     return flat.to(device) if device is not None else flat
 
 
+class Book:
+    """the first-done bookkeeping of a path's one-episode form (episode=True): per env first_done / ep_len (int32),
+    ep_ret / ep_cost (float32), and the number of steps the episode has made (t_base)"""
+
+    def __init__(self, env):
+        N = env.env_num
+        self.ints = torch.zeros(2, N, dtype=torch.int32, device=env.device)      # [0] = first_done, [1] = ep_len
+        self.sums = torch.zeros(2, N, dtype=torch.float32, device=env.device)    # [0] = ep_ret, [1] = ep_cost
+        self.t_base = 0
+
+    def reset(self):
+        self.ints.zero_()
+        self.sums.zero_()
+        self.t_base = 0
+
+    def c_struct(self):
+        b = FirstDoneState()
+        b.struct_size, b.t_base = C.sizeof(b), self.t_base
+        b.d_first_done, b.d_ep_len = self.ints[0].data_ptr(), self.ints[1].data_ptr()
+        b.d_ep_ret, b.d_ep_cost = self.sums[0].data_ptr(), self.sums[1].data_ptr()
+        return b
+
+
 class State:
-    """what a path keeps per engine: the one-set output slab of its env.step launches and its own count of policy steps
-    (the noise counter: 0 at construction, + T per call, not reset by reset())"""
+    """what a path keeps per engine: the one-set output slab of its env.step launches, its own count of policy steps
+    (the noise counter: 0 at construction, + T per call, not reset by reset()) and, once an episode=True call was made,
+    that form's bookkeeping (`book`: advanced by episode=True calls of the path alone, cleared by Engine.reset())"""
+    book = None
 
     def __init__(self, env):
         self.slab = env._out_slab(1)
@@ -134,6 +161,10 @@ class State:
 
     def reset(self):
         pass
+
+    def reset_book(self):
+        if self.book is not None:
+            self.book.reset()
 
 
 def begin(env, name, obs0, T):
@@ -213,4 +244,72 @@ def run(env, st, a, out, T, prepare, step_fn, check, act):
     # as rollout_policy leaves them
     env._obs, env._reward, env._done = out['obs_last'], out['rew'][-1], out['done'][-1]
     env._info = {'cost': out['cost'][-1]}
+    return out
+
+
+def run_episode(env, st, a, out, T, prepare, step_fn, check, act):
+    """The one-episode form of run(): prepare(stream), then T x (step_fn(args, book) -> env.step(act[t])) and the closing
+    step_fn at t = T.  No reset_done: the env launch is a plain step (flags = 0, nothing speculated, nothing committed)
+    and the policy step reads the env's plain observation, set 0 of the slab, as guardx_amd/episode.py does.  Adds the
+    copies of the bookkeeping and t0 to `out`; the engine is left as after a step()."""
+    book = st.book
+    if book is None:
+        book = st.book = Book(env)
+    slab = st.slab
+    a.d_obs_rd = slab[0][0].data_ptr()     # a flags = 0 step writes no obs_rd piece
+    b = book.c_struct()
+    stream = env._raw_stream(env._dev_index)
+    h, ref, bref, spec_ref = env._h, C.byref(a), C.byref(b), env._spec_ref
+    slab_fn = env._gx_step_slab
+    act_ptr, act_stride, slab_ptr = act.data_ptr(), 4 * act.shape[1] * act.shape[2], slab[6]
+    env._rd_obs = None
+    with torch.cuda.device(env.device):
+        check(prepare(stream))
+        for t in range(T):
+            a.t = t
+            rc = step_fn(ref, bref, stream)
+            if rc:
+                check(rc)
+            rc = slab_fn(h, act_ptr + t * act_stride, slab_ptr, 0, 0, spec_ref, stream)   # env.step(act_safe[t]), nothing else
+            if rc:
+                _native.check(rc)
+        a.t = T
+        check(step_fn(ref, bref, stream))
+    out['t0'] = book.t_base
+    st.steps += T
+    book.t_base += T
+    out['first_done'], out['ep_len'] = book.ints.clone().unbind(0)
+    out['ep_ret'], out['ep_cost'] = book.sums.clone().unbind(0)
+    # as a step() leaves them
+    env._obs, env._reward, env._done = out['obs_last'], out['rew'][-1], out['done'][-1]
+    env._info = {'cost': out['cost'][-1]}
+    return out
+
+
+def tail_probe(name, params, rows, act_dim, third, third_hidden, work_floats, prepare_fn, probe_fn, check):
+    """The tail of an episode=True call alone on `rows` (n, D), a float32 device tensor, through a library's
+    guardx_<library>_tail_probe: -> obs_last (the rows as they are) and val_last (the critic on the sanitised rows, 0 for a row with a
+    non-finite entry).  third: the packed third network on the rows' device; third_hidden(D, A) its hidden width or None."""
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2):
+        raise ValueError(f"{name}: rows must be a float32 (n, D) device tensor")
+    rows = rows.contiguous()
+    n, D = rows.shape
+    A = int(act_dim)
+    if n >= 2 ** 31:
+        raise ValueError(f"{name}: more than 2^31 - 1 rows")
+    params = params.to(device=rows.device, dtype=torch.float32).contiguous()
+    third = third.to(device=rows.device, dtype=torch.float32).contiguous()
+    hidden = hidden_of(params.numel(), lambda h: policy_floats(D, A, h))
+    h3 = third_hidden(third.numel(), D, A)
+    if hidden is None or h3 is None:
+        raise ValueError(f"{name}: {'params' if hidden is None else 'the third network'} does not fit {D} inputs, {A} "
+                         f"actions and a hidden width of {HIDDEN}")
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=rows.device)   # noqa: E731
+    out = dict(obs_last=new(n, D), val_last=new(n))
+    work = new(int(work_floats(D, A, hidden, h3)))
+    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(rows.device.index))
+    with torch.cuda.device(rows.device):
+        check(prepare_fn(D, A, hidden, h3, params.data_ptr(), third.data_ptr(), work.data_ptr(), stream))
+        check(probe_fn(n, D, A, hidden, h3, params.data_ptr(), third.data_ptr(), work.data_ptr(), rows.data_ptr(),
+                       out['obs_last'].data_ptr(), out['val_last'].data_ptr(), stream))
     return out

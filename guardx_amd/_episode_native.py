@@ -27,6 +27,13 @@ class GxeStepArgs(C.Structure):
     ]
 
 
+class GxeFinishCol(C.Structure):
+    """gxe_finish_col, field for field"""
+    _fields_ = [("d_src", _FP), ("d_dst", _FP), ("width", C.c_int32)]
+
+
+FINISH_MAX_COLS = 4  # GXE_FINISH_MAX_COLS
+
 _I = C.c_int32
 # every symbol include/guardx_episode.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -41,6 +48,11 @@ SYMBOLS = {
     "gxe_finish_work_floats": (C.c_int64, [_I, _I]),
     "gxe_finish": (C.c_int, [_I, _I, _I, _I, C.c_float, C.c_float] + [_FP] * 21 + [C.c_void_p]),
 }
+# gxe_finish with extra columns, declared in the same header under the library's full name (not part of the gxe_ set
+# above): (..., n_cols, gxe_finish_col*, d_qc, d_qcost, d_targetc, d_n_valid, stream)
+COLS_SYMBOLS = {
+    "guardx_episode_finish_cols": (C.c_int, [_I, _I, _I, _I, C.c_float, C.c_float] + [_FP] * 20 + [_I] + [_FP] * 5 + [C.c_void_p]),
+}
 
-_side = _sidelib.Binding("episode", "gxe", SYMBOLS, GXE_OK, "episode")
+_side = _sidelib.Binding("episode", "gxe", {**SYMBOLS, **COLS_SYMBOLS}, GXE_OK, "episode")
 LIB_PATH, load, check, GxeError = _side.path, _side.load, _side.check, _side.Error

@@ -40,5 +40,11 @@ SYMBOLS = {
                                        C.c_float, C.c_float, _FP, _FP, _FP, _FP, _FP, C.c_void_p]),
 }
 
-_side = _sidelib.Binding("lpg", "gxp", SYMBOLS, GXP_OK, "lpg")
+# the one-episode entries, declared in the same header under the library's full name (not part of the gxp_ set above)
+EPISODE_SYMBOLS = {
+    "guardx_lpg_policy_step_episode": (C.c_int, [C.POINTER(GxpStepArgs), _FP, C.c_void_p]),   # (args, gx_first_done_state*, stream)
+    "guardx_lpg_tail_probe": (C.c_int, [C.c_int32] * 5 + [_FP] * 6 + [C.c_void_p]),
+}
+
+_side = _sidelib.Binding("lpg", "gxp", {**SYMBOLS, **EPISODE_SYMBOLS}, GXP_OK, "lpg")
 LIB_PATH, load, check, GxpError = _side.path, _side.load, _side.check, _side.Error

@@ -37,5 +37,11 @@ SYMBOLS = {
     "gxl_correction_probe": (C.c_int, [C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_float, _FP, C.c_void_p]),
 }
 
-_side = _sidelib.Binding("safelayer", "gxl", SYMBOLS, GXL_OK, "safelayer")
+# the one-episode entries, declared in the same header under the library's full name (not part of the gxl_ set above)
+EPISODE_SYMBOLS = {
+    "guardx_safelayer_policy_step_episode": (C.c_int, [C.POINTER(GxlStepArgs), _FP, C.c_void_p]),   # (args, gx_first_done_state*, stream)
+    "guardx_safelayer_tail_probe": (C.c_int, [C.c_int32] * 5 + [_FP] * 6 + [C.c_void_p]),
+}
+
+_side = _sidelib.Binding("safelayer", "gxl", {**SYMBOLS, **EPISODE_SYMBOLS}, GXL_OK, "safelayer")
 LIB_PATH, load, check, GxlError = _side.path, _side.load, _side.check, _side.Error

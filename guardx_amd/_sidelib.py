@@ -7,6 +7,13 @@ import ctypes as C
 from . import build as _build
 
 
+class FirstDoneState(C.Structure):
+    """gx_first_done_state (include/guardx_safelayer.h, guardx_usl.h, guardx_lpg.h), field for field: the bookkeeping argument of the
+    guardx_<library>_policy_step_episode entries"""
+    _fields_ = [("struct_size", C.c_uint32), ("t_base", C.c_int32), ("d_first_done", C.c_void_p),
+                ("d_ep_len", C.c_void_p), ("d_ep_ret", C.c_void_p), ("d_ep_cost", C.c_void_p)]
+
+
 class Binding:
     """load / check / Error of LIBRARIES[key].  `prefix`: that of its C symbols ("gxu"); `symbols`: name -> (restype,
     argtypes); `ok`: its OK status; `label`: its name in the error text ("usl")."""

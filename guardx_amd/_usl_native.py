@@ -40,5 +40,11 @@ SYMBOLS = {
                                        C.c_int32, C.c_float, C.c_float, _FP, _FP, _FP, _FP, _FP, C.c_void_p]),
 }
 
-_side = _sidelib.Binding("usl", "gxu", SYMBOLS, GXU_OK, "usl")
+# the one-episode entries, declared in the same header under the library's full name (not part of the gxu_ set above)
+EPISODE_SYMBOLS = {
+    "guardx_usl_policy_step_episode": (C.c_int, [C.POINTER(GxuStepArgs), _FP, C.c_void_p]),   # (args, gx_first_done_state*, stream)
+    "guardx_usl_tail_probe": (C.c_int, [C.c_int32] * 5 + [_FP] * 6 + [C.c_void_p]),
+}
+
+_side = _sidelib.Binding("usl", "gxu", {**SYMBOLS, **EPISODE_SYMBOLS}, GXU_OK, "usl")
 LIB_PATH, load, check, GxuError = _side.path, _side.load, _side.check, _side.Error

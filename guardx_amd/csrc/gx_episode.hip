@@ -16,9 +16,11 @@
 // cost critic the third group of waves does nothing: the caller passes the value network's block in the cost critic's
 // place, so that gxe_prepare and the (H, H3) dispatch stay those of the other step libraries.
 //
-// Here: the LDS layout, the step kernel, the two kernels of gxe_finish and the C entry points.  The hidden layers' MFMA
-// chain, the sample / log-prob block, the transpose kernel and the host side's checks, dispatch and launches are
-// gx_step.h's, shared with the other step libraries.
+// Here: the LDS layout, the step kernel, the two kernels of gxe_finish / guardx_episode_finish_cols and the C entry points.  The
+// one-episode behaviour itself (the sanitising load, the first-done bookkeeping, the tail's rule), the hidden layers'
+// MFMA chain, the sample / log-prob block, the transpose kernel and the host side's checks, dispatch and launches are
+// gx_step.h's, shared with the other step libraries: the safelayer, USL and LPG step kernels run the same device code
+// in their one-episode form.
 #include "../../include/guardx_episode.h"
 #include "gx_step.h"
 #include <cstring>
@@ -61,17 +63,11 @@ GX_HD Lds lds_layout(int D, int A, int H, int HC)
 }
 size_t lds_bytes(int D, int A, int H, int HC) { return sizeof(float) * (size_t)lds_layout(D, A, H, HC).total; }
 
-// NaN, +Inf and -Inf: the exponent field is all ones
-GX_D bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// the kernel's view of gxe_step_args: this step's row blocks resolved on the host
+// the kernel's view of gxe_step_args: this step's row blocks resolved on the host (c.ep: always the one-episode form)
 struct StepArgs {
     StepCommon c;
     int D, A, has_vc;
-    int k;                            // t_base + t: the 1-based index of the step just made
     const float* vcp;
-    int *first_done, *ep_len;
-    float *ep_ret, *ep_cost;
     float* vc;                        // row block t (tail: vc_last)
 };
 
@@ -100,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void episode_step_kernel(StepArgs sa)
     const Mlp2Head hv = mlp2_head_view(lds + L.headV, 1, H);
     const Mlp2Head hc = mlp2_head_view(lds + L.headC, 1, HC);
 
-    // prologue: the first-done bookkeeping of the step just made (trpo.py:473-501).  One thread owns an env's state.
+    // prologue: the first-done bookkeeping of the step just made (gx_step.h:episode_book).  One thread owns an env's state.
     if (a.prologue && tid < kEnv) {
         const int env = env0 + tid;
         if (env < a.N) {
@@ -108,27 +104,10 @@ __global__ __launch_bounds__(kThreads) void episode_step_kernel(StepArgs sa)
             a.rew_p[env] = rew;
             a.cost_p[env] = cost;
             a.done_p[env] = done;
-            if (sa.first_done[env] == 0) {
-                sa.ep_ret[env] = sa.ep_ret[env] + rew;
-                sa.ep_cost[env] = sa.ep_cost[env] + cost;
-                sa.ep_len[env] = sa.k;
-                if (done > 0.0f) sa.first_done[env] = sa.k;
-            }
+            episode_book(a.ep, env, rew, cost, done);
         }
     }
-    // the rows: what the networks read has its non-finite entries zeroed (trpo.py:453-454), and that is what obs[t]
-    // keeps; the tail's obs_last is the row as it is
-    for (int i = tid; i < kEnv * XS; i += kThreads) {
-        const int e = i / XS, k = i - e * XS;
-        const int env = env0 + e;
-        float x = 0.0f;
-        if (k < D && env < a.N) {
-            const float raw = a.obs_rd[(size_t)env * D + k];
-            x = non_finite(raw) ? 0.0f : raw;
-            a.obs[(size_t)env * D + k] = a.tail ? raw : x;
-        }
-        X[i] = x;
-    }
+    stage_rows(a, D, XS, X, env0, tid, kThreads); // sanitised; the tail's obs_last raw
     wg_sync_lds(); // rows and heads
 
     const bool skip = (a.tail && net == 0) || (net == 2 && !sa.has_vc); // the bootstrap needs the critics only
@@ -163,11 +142,7 @@ __global__ __launch_bounds__(kThreads) void episode_step_kernel(StepArgs sa)
         const int e = tid, env = env0 + e;
         if (env < a.N) {
             float v = outs[e * (A + 2) + A], vc = sa.has_vc ? outs[e * (A + 2) + A + 1] : 0.0f;
-            if (a.tail) { // a row with a non-finite entry is not bootstrapped (trpo.py:513-521)
-                bool bad = false;
-                for (int k = 0; k < D; ++k) bad = bad || non_finite(a.obs_rd[(size_t)env * D + k]);
-                if (bad) v = vc = 0.0f;
-            }
+            if (tail_row_unusable(a, D, env)) v = vc = 0.0f;
             a.val[env] = v;
             if (sa.has_vc) sa.vc[env] = vc;
             if (!a.tail) sample_row(a, A, gls, env, outs + e * (A + 2), nullptr);
@@ -265,6 +240,20 @@ __global__ __launch_bounds__(kFinEnvs) void finish_gae_kernel(int N, int T, cons
     if (threadIdx.x == 0) reinterpret_cast<int*>(work + w.bsum)[blockIdx.x] = total;
 }
 
+// what guardx_episode_finish_cols adds to the gather launch (n == 0, qc == null: gxe_finish): extra time-major columns
+// src [T][N][w] -> dst [.][w], and USL's / LPG's target targetc[t] = cost[t] + gamma qc[t + 1], one fp32 multiply and one
+// fp32 add, the product taken as +0 at t + 1 == L (usl_one_episode/usl.py:105-107)
+constexpr int kMaxCols = GXE_FINISH_MAX_COLS;
+struct FinCols {
+    int n;
+    int w[kMaxCols];
+    const float* src[kMaxCols];
+    float* dst[kMaxCols];
+    const float *qc, *qcost;
+    float* targetc;
+    float gamma;
+};
+
 // launch 2, one block per env: its offset (the lengths before it: whole blocks of launch 1, then its own block's envs),
 // then its L rows gathered from the time-major tensors into the compacted env-major ones, the advantages normalised on
 // the way.  The block of the last env also writes the total.
@@ -275,7 +264,7 @@ __global__ __launch_bounds__(256) void finish_gather_kernel(int N, int T, int D,
                                                             float* __restrict__ mu_c, float* __restrict__ logp_c,
                                                             float* __restrict__ ret_c, float* __restrict__ adv_c,
                                                             float* __restrict__ cret_c, float* __restrict__ adc_c,
-                                                            int* __restrict__ n_valid)
+                                                            int* __restrict__ n_valid, FinCols x)
 {
     __shared__ int offset;
     if (threadIdx.x == 0) offset = 0;
@@ -312,6 +301,20 @@ __global__ __launch_bounds__(256) void finish_gather_kernel(int N, int T, int D,
         else if (k < D + A) act_c[o * A + (k - D)] = act[i * A + (k - D)];
         else mu_c[o * A + (k - D - A)] = mu[i * A + (k - D - A)];
     }
+    for (int c = 0; c < x.n; ++c) { // uniform
+        const int w = x.w[c];
+        const float* src = x.src[c];
+        float* dst = x.dst[c];
+        for (long long j = tid; j < (long long)L * w; j += 256) {
+            const int t = (int)(j / w), k = (int)(j - (long long)t * w);
+            dst[(off + t) * w + k] = src[((size_t)t * N + env) * w + k];
+        }
+    }
+    if (x.qc)
+        for (int t = tid; t < L; t += 256) {
+            const float next = t + 1 < L ? __fmul_rn(x.gamma, x.qc[(size_t)(t + 1) * N + env]) : 0.0f;
+            x.targetc[off + t] = __fadd_rn(x.qcost[(size_t)t * N + env], next);
+        }
 }
 
 __global__ void zero_count_kernel(int* n_valid) { *n_valid = 0; }
@@ -345,10 +348,8 @@ extern "C" gxe_status gxe_policy_step(const gxe_step_args* g, void* stream)
     StepArgs a;
     const size_t tn = fill_common(*g, g->D, a.c);
     a.D = g->D; a.A = g->A; a.has_vc = g->has_vc != 0;
-    a.k = g->t_base + g->t;
+    fill_book(g, g->t, a.c); // (gxe_step_args carries the bookkeeping's fields itself)
     a.vcp = g->d_vc_params;
-    a.first_done = g->d_first_done; a.ep_len = g->d_ep_len;
-    a.ep_ret = g->d_ep_ret; a.ep_cost = g->d_ep_cost;
     a.vc = !a.has_vc ? nullptr : (a.c.tail ? g->d_vc_last : g->d_vc + tn);
     return q_launch(fail, "gxe_policy_step", q_kernel_for<StepKernel>(g->hidden, g->vc_hidden), g->N, kThreads, a,
                     lds_bytes(g->D, g->A, g->hidden, g->vc_hidden), stream);
@@ -367,9 +368,7 @@ extern "C" gxe_status gxe_tail_probe(int32_t n, int32_t D, int32_t A, int32_t hi
     if (n == 0) return GXE_OK;
     StepArgs a;
     memset(&a, 0, sizeof a);
-    a.c.N = n; a.c.tail = 1; a.c.prologue = 0;
-    a.c.params = d_params; a.c.wt = d_work; a.c.obs_rd = d_rows;
-    a.c.obs = d_obs_last; a.c.val = d_val_last;
+    fill_tail_probe(a.c, n, d_params, d_work, d_rows, d_obs_last, d_val_last);
     a.D = D; a.A = A; a.has_vc = has_vc != 0;
     a.vcp = d_vc_params;
     a.vc = a.has_vc ? d_vc_last : nullptr;
@@ -381,14 +380,15 @@ extern "C" int64_t gxe_finish_work_floats(int32_t N, int32_t T)
     return (N >= 0 && T >= 1) ? (int64_t)fin_work((size_t)N, (size_t)T).total : -1;
 }
 
-extern "C" gxe_status gxe_finish(int32_t N, int32_t T, int32_t D, int32_t A, float gamma, float lam, int32_t* d_first_done,
-                                 const float* d_obs, const float* d_act, const float* d_mu, const float* d_logp,
-                                 const float* d_rew, const float* d_val, const float* d_val_last, const float* d_cost,
-                                 const float* d_vc, const float* d_vc_last, float* d_work, float* d_obs_c, float* d_act_c,
-                                 float* d_mu_c, float* d_logp_c, float* d_ret, float* d_adv, float* d_cost_ret, float* d_adc,
-                                 int32_t* d_n_valid, void* stream)
+namespace {
+
+// gxe_finish (x.n == 0, no target) and guardx_episode_finish_cols under their own names
+gxe_status finish(const char* who, int32_t N, int32_t T, int32_t D, int32_t A, float gamma, float lam, int32_t* d_first_done,
+                  const float* d_obs, const float* d_act, const float* d_mu, const float* d_logp, const float* d_rew,
+                  const float* d_val, const float* d_val_last, const float* d_cost, const float* d_vc, const float* d_vc_last,
+                  float* d_work, float* d_obs_c, float* d_act_c, float* d_mu_c, float* d_logp_c, float* d_ret, float* d_adv,
+                  float* d_cost_ret, float* d_adc, int32_t* d_n_valid, const FinCols& x, void* stream)
 {
-    const char* who = "gxe_finish";
     if (N < 0 || T < 1 || D < 1 || A < 1) return fail(GXE_ERR_ARG, std::string(who) + ": N must be >= 0, T, D and A >= 1");
     if ((int64_t)N * T > 0x7fffffffLL) return fail(GXE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 rows");
     if (!d_first_done || !d_obs || !d_act || !d_mu || !d_logp || !d_rew || !d_val || !d_val_last || !d_work || !d_obs_c ||
@@ -408,6 +408,45 @@ extern "C" gxe_status gxe_finish(int32_t N, int32_t T, int32_t D, int32_t A, flo
     if (st != GXE_OK) return st;
     hipLaunchKernelGGL(finish_gather_kernel, dim3((unsigned)N), dim3(256), 0, s, N, T, D, A, d_obs, d_act, d_mu, d_logp,
                        (const float*)d_work, n_cost ? 1 : 0, d_obs_c, d_act_c, d_mu_c, d_logp_c, d_ret, d_adv, d_cost_ret, d_adc,
-                       (int*)d_n_valid);
+                       (int*)d_n_valid, x);
     return q_launched(fail, who, hipGetLastError());
+}
+
+} // namespace
+
+extern "C" gxe_status gxe_finish(int32_t N, int32_t T, int32_t D, int32_t A, float gamma, float lam, int32_t* d_first_done,
+                                 const float* d_obs, const float* d_act, const float* d_mu, const float* d_logp,
+                                 const float* d_rew, const float* d_val, const float* d_val_last, const float* d_cost,
+                                 const float* d_vc, const float* d_vc_last, float* d_work, float* d_obs_c, float* d_act_c,
+                                 float* d_mu_c, float* d_logp_c, float* d_ret, float* d_adv, float* d_cost_ret, float* d_adc,
+                                 int32_t* d_n_valid, void* stream)
+{
+    return finish("gxe_finish", N, T, D, A, gamma, lam, d_first_done, d_obs, d_act, d_mu, d_logp, d_rew, d_val, d_val_last,
+                  d_cost, d_vc, d_vc_last, d_work, d_obs_c, d_act_c, d_mu_c, d_logp_c, d_ret, d_adv, d_cost_ret, d_adc,
+                  d_n_valid, FinCols{}, stream);
+}
+
+extern "C" gxe_status guardx_episode_finish_cols(int32_t N, int32_t T, int32_t D, int32_t A, float gamma, float lam, int32_t* d_first_done,
+                                      const float* d_obs, const float* d_act, const float* d_mu, const float* d_logp,
+                                      const float* d_rew, const float* d_val, const float* d_val_last, const float* d_cost,
+                                      const float* d_vc, const float* d_vc_last, float* d_work, float* d_obs_c, float* d_act_c,
+                                      float* d_mu_c, float* d_logp_c, float* d_ret, float* d_adv, float* d_cost_ret,
+                                      float* d_adc, int32_t n_cols, const gxe_finish_col* cols, const float* d_qc,
+                                      const float* d_qcost, float* d_targetc, int32_t* d_n_valid, void* stream)
+{
+    const char* who = "guardx_episode_finish_cols";
+    if (n_cols < 0 || n_cols > kMaxCols) return fail(GXE_ERR_ARG, std::string(who) + ": n_cols must be in 0 .. GXE_FINISH_MAX_COLS");
+    if (n_cols > 0 && !cols) return fail(GXE_ERR_ARG, std::string(who) + ": null column list");
+    FinCols x = {};
+    x.n = n_cols;
+    for (int c = 0; c < n_cols; ++c) {
+        if (!cols[c].d_src || !cols[c].d_dst || cols[c].width < 1)
+            return fail(GXE_ERR_ARG, std::string(who) + ": a column needs a source, a destination and a width >= 1");
+        x.src[c] = cols[c].d_src; x.dst[c] = cols[c].d_dst; x.w[c] = cols[c].width;
+    }
+    const int n_q = !!d_qc + !!d_qcost + !!d_targetc;
+    if (n_q != 0 && n_q != 3) return fail(GXE_ERR_ARG, std::string(who) + ": the target's pointers are all given or all null");
+    x.qc = d_qc; x.qcost = d_qcost; x.targetc = d_targetc; x.gamma = gamma;
+    return finish(who, N, T, D, A, gamma, lam, d_first_done, d_obs, d_act, d_mu, d_logp, d_rew, d_val, d_val_last, d_cost, d_vc,
+                  d_vc_last, d_work, d_obs_c, d_act_c, d_mu_c, d_logp_c, d_ret, d_adv, d_cost_ret, d_adc, d_n_valid, x, stream);
 }

@@ -180,20 +180,45 @@ extern "C" gxp_status gxp_prepare(int32_t D, int32_t A, int32_t hidden, int32_t 
     return q_prepare<StepKernel>(fail, "gxp_prepare", D, A, hidden, c_hidden, d_params, d_c_params, d_work, stream);
 }
 
-extern "C" gxp_status gxp_policy_step(const gxp_step_args* g, void* stream)
+namespace {
+
+// gxp_policy_step (book == null) and guardx_lpg_policy_step_episode under their own names
+gxp_status policy_step(const char* who, const gxp_step_args* g, const gx_first_done_state* book, bool episode, void* stream)
 {
-    const gxp_status st = q_check_common(
-        fail, "gxp_policy_step", g, [](const gxp_step_args&) { return true; }, "",
+    gxp_status st = q_check_common(
+        fail, who, g, [](const gxp_step_args&) { return true; }, "",
         [](const gxp_step_args& g, bool tail) { return g.d_q_init && (tail || g.d_lam); });
+    if (st == GXP_OK && episode) st = check_book(fail, who, book);
     if (st != GXP_OK || g->N == 0) return st;
     StepArgs a;
     const size_t tn = q_fill_common(*g, a.c);
+    fill_book(book, g->t, a.c);
     a.store = g->t == 0 && g->store_init != 0;
     a.sign = g->step_sign;
     a.q_init = g->d_q_init;
     a.lam = a.c.tail ? nullptr : g->d_lam + tn;
-    return q_launch(fail, "gxp_policy_step", q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, kThreads, a,
+    return q_launch(fail, who, q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, kThreads, a,
                     step_lds_bytes(g->D, g->A, g->hidden, g->c_hidden), stream);
+}
+
+} // namespace
+
+extern "C" gxp_status gxp_policy_step(const gxp_step_args* g, void* stream)
+{
+    return policy_step("gxp_policy_step", g, nullptr, false, stream);
+}
+
+extern "C" gxp_status guardx_lpg_policy_step_episode(const gxp_step_args* g, const gx_first_done_state* book, void* stream)
+{
+    return policy_step("guardx_lpg_policy_step_episode", g, book, true, stream);
+}
+
+extern "C" gxp_status guardx_lpg_tail_probe(int32_t n, int32_t D, int32_t A, int32_t hidden, int32_t c_hidden, const float* d_params,
+                                     const float* d_c_params, const float* d_work, const float* d_rows, float* d_obs_last,
+                                     float* d_val_last, void* stream)
+{
+    return q_tail_probe<StepKernel, StepArgs>(fail, "guardx_lpg_tail_probe", n, D, A, hidden, c_hidden, d_params, d_c_params, d_work,
+                                              d_rows, d_obs_last, d_val_last, stream);
 }
 
 extern "C" gxp_status gxp_projection_probe(int32_t n, int32_t D, int32_t A, int32_t c_hidden, const float* d_c_params,

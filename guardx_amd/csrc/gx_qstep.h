@@ -78,25 +78,18 @@ GX_D bool q_step_front(float* lds, const Lds& L, const QStepCommon& a, int tid)
     const Mlp2Head hp = mlp2_head_view(lds + L.headP, A, H);
     const Mlp2Head hv = mlp2_head_view(lds + L.headV, 1, H);
 
-    // prologue: the copies of the step just made
+    // prologue: the copies of the step just made and, in the one-episode form, its first-done bookkeeping
     if (a.prologue && tid < kEnv) {
         const int env = env0 + tid;
         if (env < a.N) {
-            a.rew_p[env] = a.rew_in[env];
-            a.cost_p[env] = a.cost_in[env];
-            a.done_p[env] = a.done_in[env];
+            const float rew = a.rew_in[env], cost = a.cost_in[env], done = a.done_in[env];
+            a.rew_p[env] = rew;
+            a.cost_p[env] = cost;
+            a.done_p[env] = done;
+            if (a.ep.on) episode_book(a.ep, env, rew, cost, done);
         }
     }
-    for (int i = tid; i < kEnv * XS; i += kThreads) {
-        const int e = i / XS, k = i - e * XS;
-        const int env = env0 + e;
-        float x = 0.0f;
-        if (k < D && env < a.N) {
-            x = a.obs_rd[(size_t)env * D + k];
-            a.obs[(size_t)env * D + k] = x;
-        }
-        X[i] = x;
-    }
+    stage_rows(a, D, XS, X, env0, tid, kThreads); // (sanitised in the one-episode form: what c_net reads as well)
     wg_sync_lds(); // rows and heads
 
     const float* wtn = a.wt + (size_t)net * wt_floats(D, H); // (net 2 starts after the two H-wide networks)
@@ -125,7 +118,7 @@ GX_D bool q_step_front(float* lds, const Lds& L, const QStepCommon& a, int tid)
     if (tid < kEnv) {
         const int e = tid, env = env0 + e;
         if (env < a.N) {
-            a.val[env] = outs[e * OS + A];
+            a.val[env] = tail_row_unusable(a, D, env) ? 0.0f : outs[e * OS + A];
             if (!a.tail) sample_row(a, A, gls, env, outs + e * OS, lds + L.q.act + e * kAS);
         }
     }
@@ -215,6 +208,25 @@ Status q_check_common(FailFn<Status> fail, const char* who, const G* g, OwnRange
 {
     return check_common(fail, who, g, kRowD, step_lds_bytes, &G::D, &G::c_hidden, &G::d_c_params, own_range, own_text,
                         [&](const G& s, bool tail) { return (tail || (s.d_act_safe && s.d_qc)) && own_ptrs(s, tail); });
+}
+
+// guardx_<library>_tail_probe: the tail launch alone on n caller-supplied rows, on the library's step kernels (StepK); A: its
+// StepArgs, whose member c is the QStepCommon
+template <class StepK, class A, class Status>
+Status q_tail_probe(FailFn<Status> fail, const char* who, int n, int D, int Aw, int hidden, int c_hidden, const float* d_params,
+                    const float* d_c_params, const float* d_work, const float* d_rows, float* d_obs_last, float* d_val_last,
+                    void* stream)
+{
+    if (n < 0) return fail(Status(kErrArg), std::string(who) + ": n must be >= 0");
+    const Status st = check_shape(fail, who, kRowD, step_lds_bytes, D, Aw, hidden, c_hidden);
+    if (st != Status(kOk)) return st;
+    if (!d_params || !d_c_params || !d_work || !d_rows || !d_obs_last || !d_val_last)
+        return fail(Status(kErrArg), std::string(who) + ": null pointer");
+    if (n == 0) return Status(kOk);
+    A a = {};
+    fill_tail_probe(a.c, n, d_params, d_work, d_rows, d_obs_last, d_val_last);
+    a.c.q = q_args(D, Aw, false, 0.0f, 0.0f, d_c_params, d_work + 2 * wt_floats(D, hidden));
+    return q_launch(fail, who, q_kernel_for<StepK>(hidden, c_hidden), n, kThreads, a, step_lds_bytes(D, Aw, hidden, c_hidden), stream);
 }
 
 // the shared fields of a checked gx?_step_args; returns the offset of row block t in a [T][N] array (0 in the tail)

@@ -20,6 +20,10 @@
 // workgroups on 256 CUs: the launch is bound by latency, which is why the three networks run side by side, each on four
 // waves.
 //
+// The one-episode form (guardx_safelayer_policy_step_episode, the `safelayer_one_episode` learner) is the same kernel under the
+// uniform argument StepCommon::ep.on: the rows sanitised, the first-done bookkeeping after the prologue's copies
+// (gx_step.h), prev_c = the step's cost whatever `done` says, and the tail's no-bootstrap rule.
+//
 // Here: the LDS layout, the correction, the kernel and the C entry points.  The hidden layers' MFMA chain, the sample /
 // log-prob block, the transpose kernel and the host side's checks, dispatch and launches are gx_step.h's, shared with
 // the other step libraries.
@@ -136,32 +140,26 @@ __global__ __launch_bounds__(kThreads) void safelayer_step_kernel(StepArgs sa)
     const Mlp2Head hg = mlp2_head_view(lds + L.headG, A, HG);
 
     // prologue: the prev_c update of the step just made (safelayer.py:546, 576-581).  The thread that updates env's
-    // prev_c here is the one that reads it below (tid < kEnv, env = env0 + tid): program order, no fence.
+    // prev_c here is the one that reads it below (tid < kEnv, env = env0 + tid): program order, no fence.  In the
+    // one-episode form nothing is re-initialised at a done, so prev_c is the step's cost whatever `done` says
+    // (safelayer_one_episode/safelayer.py:553), and the first-done bookkeeping follows the copies.
     float prev_c = 0.0f;
     if (tid < kEnv) {
         const int env = env0 + tid;
         if (env < a.N) {
-            prev_c = sa.prev_c[env];
             if (a.prologue) {
-                const float cost = a.cost_in[env], done = a.done_in[env];
-                a.rew_p[env] = a.rew_in[env];
+                const float rew = a.rew_in[env], cost = a.cost_in[env], done = a.done_in[env];
+                a.rew_p[env] = rew;
                 a.cost_p[env] = cost;
                 a.done_p[env] = done;
-                prev_c = done > 0.0f ? 0.0f : cost;
+                if (a.ep.on) episode_book(a.ep, env, rew, cost, done);
+                prev_c = (done > 0.0f && !a.ep.on) ? 0.0f : cost;
                 sa.prev_c[env] = prev_c;
-            }
+            } else if (!a.tail)
+                prev_c = sa.prev_c[env];
         }
     }
-    for (int i = tid; i < kEnv * XS; i += kThreads) {
-        const int e = i / XS, k = i - e * XS;
-        const int env = env0 + e;
-        float x = 0.0f;
-        if (k < D && env < a.N) {
-            x = a.obs_rd[(size_t)env * D + k];
-            a.obs[(size_t)env * D + k] = x;
-        }
-        X[i] = x;
-    }
+    stage_rows(a, D, XS, X, env0, tid, kThreads); // (sanitised in the one-episode form)
     wg_sync_lds(); // rows and heads
 
     const bool skip = a.tail && net != 1; // the bootstrap needs the critic only
@@ -200,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void safelayer_step_kernel(StepArgs sa)
         const int e = tid, env = env0 + e;
         if (env < a.N) {
             float* oe = outs + e * OS;
-            a.val[env] = oe[A];
+            a.val[env] = tail_row_unusable(a, D, env) ? 0.0f : oe[A];
             if (!a.tail) {
                 sample_row(a, A, gls, env, oe, oe + 2 * A + 1);
                 sa.prev_cost[env] = prev_c;
@@ -237,15 +235,20 @@ extern "C" gxl_status gxl_prepare(int32_t D, int32_t A, int32_t hidden, int32_t 
     return prepare<StepKernel>(fail, "gxl_prepare", kRowD, lds_bytes, D, A, hidden, g_hidden, D, d_params, d_g_params, d_work, stream);
 }
 
-extern "C" gxl_status gxl_policy_step(const gxl_step_args* g, void* stream)
+namespace {
+
+// gxl_policy_step (book == null) and guardx_safelayer_policy_step_episode under their own names
+gxl_status policy_step(const char* who, const gxl_step_args* g, const gx_first_done_state* book, bool episode, void* stream)
 {
-    const gxl_status st = check_common(
-        fail, "gxl_policy_step", g, kRowD, lds_bytes, &gxl_step_args::D, &gxl_step_args::g_hidden, &gxl_step_args::d_g_params,
+    gxl_status st = check_common(
+        fail, who, g, kRowD, lds_bytes, &gxl_step_args::D, &gxl_step_args::g_hidden, &gxl_step_args::d_g_params,
         [](const gxl_step_args&) { return true; }, "",
         [](const gxl_step_args& g, bool tail) { return g.d_prev_c && (tail || (g.d_act_safe && g.d_g && g.d_prev_cost)); });
+    if (st == GXL_OK && episode) st = check_book(fail, who, book);
     if (st != GXL_OK || g->N == 0) return st;
     StepArgs a;
     const size_t tn = fill_common(*g, g->D, a.c), A = (size_t)g->A;
+    fill_book(book, g->t, a.c);
     a.D = g->D; a.A = g->A; a.correct = g->correct != 0;
     a.delta = g->delta;
     a.gp = g->d_g_params;
@@ -253,8 +256,38 @@ extern "C" gxl_status gxl_policy_step(const gxl_step_args* g, void* stream)
     a.act_safe = a.c.tail ? nullptr : g->d_act_safe + tn * A;
     a.g = a.c.tail ? nullptr : g->d_g + tn * A;
     a.prev_cost = a.c.tail ? nullptr : g->d_prev_cost + tn;
-    return q_launch(fail, "gxl_policy_step", q_kernel_for<StepKernel>(g->hidden, g->g_hidden), g->N, kThreads, a,
+    return q_launch(fail, who, q_kernel_for<StepKernel>(g->hidden, g->g_hidden), g->N, kThreads, a,
                     lds_bytes(g->D, g->A, g->hidden, g->g_hidden), stream);
+}
+
+} // namespace
+
+extern "C" gxl_status gxl_policy_step(const gxl_step_args* g, void* stream)
+{
+    return policy_step("gxl_policy_step", g, nullptr, false, stream);
+}
+
+extern "C" gxl_status guardx_safelayer_policy_step_episode(const gxl_step_args* g, const gx_first_done_state* book, void* stream)
+{
+    return policy_step("guardx_safelayer_policy_step_episode", g, book, true, stream);
+}
+
+extern "C" gxl_status guardx_safelayer_tail_probe(int32_t n, int32_t D, int32_t A, int32_t hidden, int32_t g_hidden, const float* d_params,
+                                     const float* d_g_params, const float* d_work, const float* d_rows, float* d_obs_last,
+                                     float* d_val_last, void* stream)
+{
+    const char* who = "guardx_safelayer_tail_probe";
+    if (n < 0) return fail(GXL_ERR_ARG, std::string(who) + ": n must be >= 0");
+    const gxl_status st = check_shape(fail, who, kRowD, lds_bytes, D, A, hidden, g_hidden);
+    if (st != GXL_OK) return st;
+    if (!d_params || !d_g_params || !d_work || !d_rows || !d_obs_last || !d_val_last)
+        return fail(GXL_ERR_ARG, std::string(who) + ": null pointer");
+    if (n == 0) return GXL_OK;
+    StepArgs a = {};
+    fill_tail_probe(a.c, n, d_params, d_work, d_rows, d_obs_last, d_val_last);
+    a.D = D; a.A = A;
+    a.gp = d_g_params;
+    return q_launch(fail, who, q_kernel_for<StepKernel>(hidden, g_hidden), n, kThreads, a, lds_bytes(D, A, hidden, g_hidden), stream);
 }
 
 extern "C" gxl_status gxl_correction_probe(int32_t n, int32_t A, const float* d_g, const float* d_a, const float* d_prev_c,

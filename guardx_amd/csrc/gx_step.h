@@ -1,10 +1,11 @@
-// gx_step.h -- what the four step libraries (gx_statewise.hip, gx_safelayer.hip, and through gx_qstep.h gx_usl.hip and
-// gx_lpg.hip) share that is not about a Q critic.  Each runs `ac.step` on the device between two env.step launches, 16
+// gx_step.h -- what the five step libraries (gx_statewise.hip, gx_safelayer.hip, gx_episode.hip, and through gx_qstep.h
+// gx_usl.hip and gx_lpg.hip) share that is not about a Q critic.  Each runs `ac.step` on the device between two env.step launches, 16
 // envs per workgroup, on three two-hidden-layer tanh networks whose hidden layers gx?_prepare transposes into a workspace.
 // Device: the sizes, Softplus, the transpose kernel, the pipelined MFMA chain of a hidden layer, the Gaussian sample /
-// log-prob block of ac.step on a row and the logstd write.  Host: the shape check, the (H, H3) kernel dispatch, the LDS
+// log-prob block of ac.step on a row, the logstd write and the one-episode form of a step (the sanitising load of the
+// rows, the first-done bookkeeping, the tail's no-bootstrap rule).  Host: the shape check, the (H, H3) kernel dispatch, the LDS
 // cap, gx?_prepare, the checks and the row-block arithmetic of gx?_policy_step, the launches.  The host functions are
-// templates over the library's status enum (the four enums have equal values) and its public gx?_step_args (equal names
+// templates over the library's status enum (the enums have equal values) and its public gx?_step_args (equal names
 // for every shared field); they report through the library's own `fail`, passed first.  What differs between the
 // libraries comes in as values; nothing here asks which library is calling.
 // One translation unit per library: everything sits in an unnamed namespace.
@@ -68,10 +69,20 @@ __global__ void step_transpose_kernel(const float* __restrict__ params, const fl
     }
 }
 
+// The one-episode form of a step (the `*_one_episode` learners, safe_rl_libX/trpo_one_episode/trpo.py:450-545: no
+// reset_done, the rows sanitised, the first-done bookkeeping).  on: uniform over the launch; the rest is read only where
+// it is set.  k = t_base + t, the 1-based index in the episode of the step just made.
+struct EpisodeBook {
+    int on, k;
+    int *first_done, *ep_len;
+    float *ep_ret, *ep_cost;
+};
+
 // what every step kernel's view of a gx?_step_args holds: this step's row blocks resolved on the host
 struct StepCommon {
     int N, env_offset;
     int tail, prologue;
+    EpisodeBook ep;
     uint32_t seed0, seed1, tnoise;
     const float *params, *wt;
     const float* obs_rd;              // [N][the env's own observation width]
@@ -106,6 +117,49 @@ GX_D void sample_row(const StepCommon& a, int A, const float* gls, int env, cons
         }
     }
     a.logp[env] = lp;
+}
+
+// NaN, +Inf and -Inf: the exponent field is all ones
+GX_D bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// The rows of the workgroup's 16 envs into the X tile [16][XS] (columns D .. and rows past N zero) and through to row
+// block t of obs, by all `threads` threads.  In the one-episode form what the networks read has its non-finite entries
+// replaced by +0.0f (trpo.py:453-454), and that is what obs[t] keeps; the tail's obs_last is the row as it is.
+GX_D void stage_rows(const StepCommon& a, int D, int XS, float* X, int env0, int tid, int threads)
+{
+    for (int i = tid; i < kEnv * XS; i += threads) {
+        const int e = i / XS, k = i - e * XS;
+        const int env = env0 + e;
+        float x = 0.0f;
+        if (k < D && env < a.N) {
+            const float raw = a.obs_rd[(size_t)env * D + k];
+            x = (a.ep.on && non_finite(raw)) ? 0.0f : raw;
+            a.obs[(size_t)env * D + k] = a.tail ? raw : x;
+        }
+        X[i] = x;
+    }
+}
+
+// The first-done bookkeeping of the step just made, by the thread that owns env's state (trpo.py:473-501): reward and
+// cost are summed up to and including the step that finishes the env, one fp32 add each.
+GX_D void episode_book(const EpisodeBook& b, int env, float rew, float cost, float done)
+{
+    if (b.first_done[env] == 0) {
+        b.ep_ret[env] = b.ep_ret[env] + rew;
+        b.ep_cost[env] = b.ep_cost[env] + cost;
+        b.ep_len[env] = b.k;
+        if (done > 0.0f) b.first_done[env] = b.k;
+    }
+}
+
+// The tail's rule in the one-episode form: a row with a non-finite entry is not bootstrapped (the intent of
+// trpo.py:513-521).  True for such a row of env; false in every other launch.
+GX_D bool tail_row_unusable(const StepCommon& a, int D, int env)
+{
+    bool bad = false;
+    if (a.tail && a.ep.on)
+        for (int k = 0; k < D; ++k) bad = bad || non_finite(a.obs_rd[(size_t)env * D + k]);
+    return bad;
 }
 
 // logstd as the learner stores it, log(exp(log_std)): written once, by the second wave of workgroup 0
@@ -328,6 +382,7 @@ size_t fill_common(const G& g, int D, StepCommon& c)
     const size_t N = (size_t)g.N, A = (size_t)g.A;
     c.N = g.N; c.env_offset = g.env_offset;
     c.tail = g.t == g.T; c.prologue = g.t > 0;
+    c.ep = EpisodeBook{}; // the reset_done form; fill_book sets the other
     c.seed0 = g.seed[0]; c.seed1 = g.seed[1]; c.tnoise = g.step0 + (uint32_t)g.t;
     c.params = g.d_params; c.wt = g.d_work;
     c.obs_rd = c.prologue ? g.d_obs_rd : g.d_obs0;
@@ -344,6 +399,39 @@ size_t fill_common(const G& g, int D, StepCommon& c)
     c.obs = g.d_obs + tn * (size_t)D; c.act = g.d_act + tn * A; c.mu = g.d_mu + tn * A;
     c.logp = g.d_logp + tn; c.val = g.d_val + tn; c.logstd = g.d_logstd;
     return tn;
+}
+
+// The checks of a guardx_<library>_policy_step_episode entry on its bookkeeping argument (gx_first_done_state), after those
+// of gx?_policy_step on the step arguments and before anything is launched.
+template <class Status, class Book>
+Status check_book(FailFn<Status> fail, const char* who, const Book* b)
+{
+    const std::string w(who);
+    if (!b) return fail(Status(kErrArg), w + ": null bookkeeping struct");
+    if (b->struct_size != sizeof(Book)) return fail(Status(kErrArg), w + ": bookkeeping struct_size mismatch");
+    if (b->t_base < 0) return fail(Status(kErrArg), w + ": t_base must be >= 0");
+    if (!b->d_first_done || !b->d_ep_len || !b->d_ep_ret || !b->d_ep_cost) return fail(Status(kErrArg), w + ": null bookkeeping pointer");
+    return Status(kOk);
+}
+
+// the one-episode form of step t (null: the reset_done form, as fill_common leaves it)
+template <class Book>
+void fill_book(const Book* b, int t, StepCommon& c)
+{
+    if (!b) return;
+    c.ep.on = 1; c.ep.k = b->t_base + t;
+    c.ep.first_done = b->d_first_done; c.ep.ep_len = b->d_ep_len;
+    c.ep.ep_ret = b->d_ep_ret; c.ep.ep_cost = b->d_ep_cost;
+}
+
+// the view of a tail launch alone on n caller-supplied rows (the guardx_<library>_tail_probe entry points): no prologue, no state
+inline void fill_tail_probe(StepCommon& c, int n, const float* params, const float* work, const float* rows, float* obs_last,
+                            float* val_last)
+{
+    c = StepCommon{};
+    c.N = n; c.tail = 1; c.ep.on = 1;
+    c.params = params; c.wt = work; c.obs_rd = rows;
+    c.obs = obs_last; c.val = val_last;
 }
 
 } // namespace

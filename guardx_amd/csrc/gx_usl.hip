@@ -188,18 +188,43 @@ extern "C" gxu_status gxu_prepare(int32_t D, int32_t A, int32_t hidden, int32_t 
     return q_prepare<StepKernel>(fail, "gxu_prepare", D, A, hidden, c_hidden, d_params, d_c_params, d_work, stream);
 }
 
-extern "C" gxu_status gxu_policy_step(const gxu_step_args* g, void* stream)
+namespace {
+
+// gxu_policy_step (book == null) and guardx_usl_policy_step_episode under their own names
+gxu_status policy_step(const char* who, const gxu_step_args* g, const gx_first_done_state* book, bool episode, void* stream)
 {
-    const gxu_status st = q_check_common(
-        fail, "gxu_policy_step", g, [](const gxu_step_args& g) { return g.niter >= 0; }, ", niter >= 0",
+    gxu_status st = q_check_common(
+        fail, who, g, [](const gxu_step_args& g) { return g.niter >= 0; }, ", niter >= 0",
         [](const gxu_step_args& g, bool tail) { return tail || g.d_iters; });
+    if (st == GXU_OK && episode) st = check_book(fail, who, book);
     if (st != GXU_OK || g->N == 0) return st;
     StepArgs a;
     const size_t tn = q_fill_common(*g, a.c);
+    fill_book(book, g->t, a.c);
     a.c.q.niter = g->niter; a.c.q.eta = g->eta;
     a.iters = a.c.tail ? nullptr : g->d_iters + tn;
-    return q_launch(fail, "gxu_policy_step", q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, kThreads, a,
+    return q_launch(fail, who, q_kernel_for<StepKernel>(g->hidden, g->c_hidden), g->N, kThreads, a,
                     step_lds_bytes(g->D, g->A, g->hidden, g->c_hidden), stream);
+}
+
+} // namespace
+
+extern "C" gxu_status gxu_policy_step(const gxu_step_args* g, void* stream)
+{
+    return policy_step("gxu_policy_step", g, nullptr, false, stream);
+}
+
+extern "C" gxu_status guardx_usl_policy_step_episode(const gxu_step_args* g, const gx_first_done_state* book, void* stream)
+{
+    return policy_step("guardx_usl_policy_step_episode", g, book, true, stream);
+}
+
+extern "C" gxu_status guardx_usl_tail_probe(int32_t n, int32_t D, int32_t A, int32_t hidden, int32_t c_hidden, const float* d_params,
+                                     const float* d_c_params, const float* d_work, const float* d_rows, float* d_obs_last,
+                                     float* d_val_last, void* stream)
+{
+    return q_tail_probe<StepKernel, StepArgs>(fail, "guardx_usl_tail_probe", n, D, A, hidden, c_hidden, d_params, d_c_params, d_work,
+                                              d_rows, d_obs_last, d_val_last, stream);
 }
 
 extern "C" gxu_status gxu_correction_probe(int32_t n, int32_t D, int32_t A, int32_t c_hidden, const float* d_c_params,

@@ -489,6 +489,9 @@ class Engine:
             self._safelayer.reset()     # prev_c = 0 (safelayer.py:507, 567)
         if self._episode is not None:
             self._episode.reset()       # first_done = ep_ret = ep_cost = ep_len = 0, the episode starts over
+        for st in (self._safelayer, self._usl, self._lpg):
+            if st is not None:
+                st.reset_book()         # the same for the episode=True form of the three safe-action rollouts
         if not check:
             self._obs = obs
             return obs
@@ -873,7 +876,7 @@ class Engine:
             raise NotImplementedError(f"g_net has {getattr(flat, _sl.G_NET_ATTR)} outputs; the action has {int(act_dim)}")
         return flat
 
-    def rollout_safelayer(self, params, T, obs0=None, noise_seed=(0, 0), *, g_net, correct=True, delta=0.0):
+    def rollout_safelayer(self, params, T, obs0=None, noise_seed=(0, 0), *, g_net, correct=True, delta=0.0, episode=False):
         """T x (ac.step -> safety correction -> env.step(act_safe) -> reset_done) on device: the safelayer learner's
         collection loop (safelayer.py:514-581; Dalal et al. 2018).  `params` = pack_actor_critic(ac), `g_net` =
         pack_g_net(ac.ccritic).  With g = g_net(obs) and pred = g.a + prev_c: act_safe = a where pred <= delta, else
@@ -885,9 +888,17 @@ class Engine:
         step t used], done (T,N), plus obs_last (N,D), val_last (N,), logstd (A,).  prev_c (the cost of the env's
         previous step, 0 after a done) persists across calls; reset() clears it; step(), rollout_policy and
         rollout_statewise neither read nor write it.  The noise counter is this path's own (0 at construction, + T per
-        call)."""
+        call).
+        episode=True is the collection loop of `safelayer_one_episode` (safelayer_one_episode/safelayer.py:493-590): T x (zero the NaN / Inf entries of obs -> ac.step
+        -> the correction -> env.step(act_safe)) with NO reset_done; a finished env keeps being stepped, and prev_c is the cost of the
+        previous step whatever its `done` says (nothing is re-initialised).  obs holds the
+        sanitised rows, obs_last the env's row as it is, val_last is 0 for a row with a non-finite entry, and the result
+        gains first_done, ep_len (int32), ep_ret, ep_cost (N,) and t0 as rollout_episode defines them.  That bookkeeping
+        is this path's own: advanced by its episode=True calls alone, kept across calls, cleared by reset().  ep_len
+        counts the steps while first_done == 0 (the reference's own ep_len is always T in these three loops; what it
+        logs as EpLen is first_done).  rollout_buffer.episode_rollout_batch turns a whole episode into the batch."""
         from . import safelayer as _sl
-        return _sl.rollout(self, params, T, g_net, obs0, noise_seed, correct, delta)
+        return _sl.rollout(self, params, T, g_net, obs0, noise_seed, correct, delta, episode)
 
     @staticmethod
     def pack_q_critic(ccritic, device=None):
@@ -900,7 +911,7 @@ class Engine:
         return _usl.pack_q_critic(ccritic, device)
 
     def rollout_usl(self, params, T, obs0=None, noise_seed=(0, 0), *, q_critic, correct=True, delta=0.0, niter=20,
-                    eta=0.05, grad_scale=None):
+                    eta=0.05, grad_scale=None, episode=False):
         """T x (ac.step -> gradient-descent correction -> env.step(act_safe) -> reset_done) on device: the USL learner's
         collection loop (usl.py:478-553, usl_core.py:165-196).  `params` = pack_actor_critic(ac), `q_critic` =
         pack_q_critic(ac.ccritic).  qc = Q(obs, act) on the sampled action; with correct=True, per row and at most niter
@@ -913,12 +924,19 @@ class Engine:
         act_safe [what env.step received], mu (T,N,A), logp, val, qc, rew, cost, done (T,N), iters (T,N) [the updates
         applied, as float32], plus obs_last (N,D), val_last (N,), logstd (A,).  The noise counter is this path's own (0
         at construction, + T per call, not reset by reset()); step(), reset() and the other rollouts neither read nor
-        advance it."""
+        advance it.
+        episode=True is the collection loop of `usl_one_episode` (usl_one_episode/usl.py:454-554): T x (zero the NaN / Inf entries of obs -> ac.step
+        -> the correction -> env.step(act_safe)) with NO reset_done; a finished env keeps being stepped.  obs holds the
+        sanitised rows, obs_last the env's row as it is, val_last is 0 for a row with a non-finite entry, and the result
+        gains first_done, ep_len (int32), ep_ret, ep_cost (N,) and t0 as rollout_episode defines them.  That bookkeeping
+        is this path's own: advanced by its episode=True calls alone, kept across calls, cleared by reset().  ep_len
+        counts the steps while first_done == 0 (the reference's own ep_len is always T in these three loops; what it
+        logs as EpLen is first_done).  rollout_buffer.episode_rollout_batch turns a whole episode into the batch."""
         from . import usl as _usl
-        return _usl.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, niter, eta, grad_scale)
+        return _usl.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, niter, eta, grad_scale, episode)
 
     def rollout_lpg(self, params, T, obs0=None, noise_seed=(0, 0), *, q_critic, correct=True, delta=0.0, store_init=True,
-                    grad_scale=None, step_sign=1.0):
+                    grad_scale=None, step_sign=1.0, episode=False):
         """T x (ac.step -> gradient projection -> env.step(act_safe) -> reset_done) on device: the LPG learner's
         collection loop (lpg.py:486-564, lpg_core.py:161-198).  `params` = pack_actor_critic(ac), `q_critic` =
         pack_q_critic(ac.ccritic) (LPG's C_Critic.c_net is USL's module).  qc = Q(obs, act) on the sampled action.
@@ -937,9 +955,17 @@ class Engine:
         applied, 0 for an uncorrected row], plus obs_last (N,D), val_last (N,), logstd (A,) and q_init (N,) [a copy of
         the values the call used].  q_init (zero at construction) persists across calls and is not cleared by reset() or
         a done env.  The noise counter is this path's own (0 at construction, + T per call, not reset by reset());
-        step(), reset() and the other rollouts neither read nor change either."""
+        step(), reset() and the other rollouts neither read nor change either.
+        episode=True is the collection loop of `lpg_one_episode` (lpg_one_episode/lpg.py:464-565): T x (zero the NaN / Inf entries of obs -> ac.step
+        -> the correction -> env.step(act_safe)) with NO reset_done; a finished env keeps being stepped.  obs holds the
+        sanitised rows, obs_last the env's row as it is, val_last is 0 for a row with a non-finite entry, and the result
+        gains first_done, ep_len (int32), ep_ret, ep_cost (N,) and t0 as rollout_episode defines them.  That bookkeeping
+        is this path's own: advanced by its episode=True calls alone, kept across calls, cleared by reset().  ep_len
+        counts the steps while first_done == 0 (the reference's own ep_len is always T in these three loops; what it
+        logs as EpLen is first_done).  rollout_buffer.episode_rollout_batch turns a whole episode into the batch."""
         from . import lpg as _lpg
-        return _lpg.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, store_init, grad_scale, step_sign)
+        return _lpg.rollout(self, params, T, q_critic, obs0, noise_seed, correct, delta, store_init, grad_scale, step_sign,
+                            episode)
 
     def rollout_episode(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (zero the NaN / Inf entries of obs -> ac.step -> env.step) on device, with NO reset_done: the collection

@@ -56,8 +56,15 @@ class State(_cl.State):
         self.q_init = env._new(env.env_num).zero_()
 
 
+def tail_probe(params, rows, act_dim, q_critic):
+    """the tail of an episode=True call alone on `rows` (n, D) (guardx_lpg_tail_probe): -> obs_last (raw), val_last"""
+    lib = _lpg_native.load()
+    return _cl.tail_probe("tail_probe", params, rows, act_dim, q_critic, _cl.q_hidden, lib.gxp_work_floats, lib.gxp_prepare,
+                          lib.guardx_lpg_tail_probe, _lpg_native.check)
+
+
 def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0, store_init=True,
-            grad_scale=None, step_sign=1.0):
+            grad_scale=None, step_sign=1.0, episode=False):
     params, cp, obs0, N, D, A, T, hidden, c_hidden = _cl.q_rollout_inputs(env, "rollout_lpg", params, q_critic, obs0, T)
     lib = _lpg_native.load()
     st = env._lpg
@@ -76,6 +83,9 @@ def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True
     def prepare(stream):
         return lib.gxp_prepare(D, A, hidden, c_hidden, a.d_params, a.d_c_params, a.d_work, stream)
 
-    _cl.run(env, st, a, out, T, prepare, lib.gxp_policy_step, _lpg_native.check, out['act_safe'])
+    if episode:   # lpg_one_episode/lpg.py:464-565: no reset_done, the rows sanitised, the first-done bookkeeping
+        _cl.run_episode(env, st, a, out, T, prepare, lib.guardx_lpg_policy_step_episode, _lpg_native.check, out['act_safe'])
+    else:
+        _cl.run(env, st, a, out, T, prepare, lib.gxp_policy_step, _lpg_native.check, out['act_safe'])
     out['q_init'] = st.q_init.clone()   # the values this call used (stream-ordered after its launches)
     return out

@@ -334,6 +334,11 @@ def episode_rollout_batch(out, gamma=0.99, lam=0.95):
     other rows are left unwritten, and n_valid.  Device tensors: two launches (gxe_finish) and ONE .item(), the only
     synchronisation.  Host tensors (a result moved to the CPU) go through the same recursion in torch, operation for
     operation, so the two agree bit for bit.
+    The episode=True results of rollout_safelayer / rollout_usl / rollout_lpg (the one-episode buffers of
+    safelayer_one_episode/safelayer.py:30-140, usl_one_episode/usl.py:22-144; LPG's is USL's) are served too, keyed on
+    what `out` holds: with out['act_safe'] also act_safe; with out['prev_cost'] also cost and prev_cost; with out['qc']
+    also cost and targetc, targetc[t] = cost[t] + gamma32 * qc[t + 1] (one fp32 multiply, one fp32 add), the product
+    taken as +0 at t + 1 == L (usl.py:105-107).  Same two launches (guardx_episode_finish_cols), same one .item().
     (The reference never re-zeroes adv_buf / adc_buf between epochs: from its second epoch on the entries past
     first_done hold the previous epoch's normalised values and leak into mean and deviation.  Here they are 0, which is
     what its first epoch sees.)"""
@@ -346,11 +351,22 @@ def episode_rollout_batch(out, gamma=0.99, lam=0.95):
         _require(out, ('cost', 'vc_last'), "episode_rollout_batch", "Engine.rollout_episode(..., cost_critic=...)")
     T, N = out['rew'].shape
     D, A = out['obs'].shape[-1], out['act'].shape[-1]
+    # the safe-action learners' extra columns: (key, width)
+    cols = [('act_safe', A)] if 'act_safe' in out else []
+    has_q = 'qc' in out
+    if 'prev_cost' in out or has_q:
+        _require(out, ('cost',), "episode_rollout_batch", "Engine.rollout_safelayer / rollout_usl / rollout_lpg(..., episode=True)")
+        cols.append(('cost', 1))
+    if 'prev_cost' in out:
+        cols.append(('prev_cost', 1))
     # gxe_finish is handed raw pointers: every tensor must have the shape the sizes above promise
     shapes = dict(obs=(T, N, D), act=(T, N, A), mu=(T, N, A), logp=(T, N), val=(T, N), val_last=(N,), first_done=(N,),
                   logstd=(A,))
     if has_cost:
         shapes.update(cost=(T, N), vc=(T, N), vc_last=(N,))
+    shapes.update({k: (T, N, A) if k == 'act_safe' else (T, N) for k, _ in cols})
+    if has_q:
+        shapes.update(qc=(T, N))
     for k, want in shapes.items():
         if tuple(out[k].shape) != want:
             raise ValueError(f"episode_rollout_batch: out['{k}'] has shape {tuple(out[k].shape)}; expected {want} "
@@ -368,6 +384,13 @@ def episode_rollout_batch(out, gamma=0.99, lam=0.95):
         if has_cost:
             adc, cost_ret = _episode_channel_host(f(out['cost']), f(out['vc']), out['vc_last'], L, finished, gamma, lam, 0)
             batch.update(cost_ret=pick(cost_ret), adc=pick(adc))
+        batch.update({k: pick(out[k]) for k, _ in cols})
+        if has_q:
+            qc = f(out['qc'])
+            q_next = torch.zeros_like(qc)
+            q_next[:-1] = torch.tensor(gamma, dtype=torch.float32) * qc[1:]
+            q_next = torch.where(torch.arange(1, T + 1).view(T, 1) < L.view(1, N), q_next, torch.zeros_like(qc))
+            batch['targetc'] = pick(f(out['cost']) + q_next)
     else:
         from . import _episode_native
         lib = _episode_native.load()
@@ -375,21 +398,31 @@ def episode_rollout_batch(out, gamma=0.99, lam=0.95):
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
         src = {k: f(out[k]) for k in ('obs', 'act', 'mu', 'logp', 'rew', 'val', 'val_last')}
         cost = {k: f(out[k]) for k in ('cost', 'vc', 'vc_last')} if has_cost else {}
+        extra = {k: f(out[k]) for k, _ in cols}
+        qsrc = {k: f(out[k]) for k in ('qc', 'cost')} if has_q else {}
         fd = out['first_done'].to(device=dev, dtype=torch.int32).contiguous()
         batch = dict(obs=new(N * T, D), act=new(N * T, A), ret=new(N * T), adv=new(N * T), logp=new(N * T), mu=new(N * T, A))
         if has_cost:
             batch.update(cost_ret=new(N * T), adc=new(N * T))
+        batch.update({k: new(N * T, w) if k == 'act_safe' else new(N * T) for k, w in cols})
+        if has_q:
+            batch['targetc'] = new(N * T)
+        carr = (_episode_native.GxeFinishCol * max(1, len(cols)))()
+        for c, (k, w) in zip(carr, cols):
+            c.d_src, c.d_dst, c.width = extra[k].data_ptr(), batch[k].data_ptr(), w
+        qp = lambda t: t.data_ptr() if has_q else None   # noqa: E731
         count = torch.empty(1, dtype=torch.int32, device=dev)
         work = new(int(lib.gxe_finish_work_floats(N, T)))
         cp = lambda k: cost[k].data_ptr() if has_cost else None   # noqa: E731
         bp = lambda k: batch[k].data_ptr() if has_cost else None   # noqa: E731
         with torch.cuda.device(dev):
-            _episode_native.check(lib.gxe_finish(
+            _episode_native.check(lib.guardx_episode_finish_cols(
                 N, T, D, A, float(gamma), float(lam), fd.data_ptr(), src['obs'].data_ptr(), src['act'].data_ptr(),
                 src['mu'].data_ptr(), src['logp'].data_ptr(), src['rew'].data_ptr(), src['val'].data_ptr(),
                 src['val_last'].data_ptr(), cp('cost'), cp('vc'), cp('vc_last'), work.data_ptr(), batch['obs'].data_ptr(),
                 batch['act'].data_ptr(), batch['mu'].data_ptr(), batch['logp'].data_ptr(), batch['ret'].data_ptr(),
-                batch['adv'].data_ptr(), bp('cost_ret'), bp('adc'), count.data_ptr(),
+                batch['adv'].data_ptr(), bp('cost_ret'), bp('adc'), len(cols), C.cast(carr, C.c_void_p) if cols else None,
+                qp(qsrc.get('qc')), qp(qsrc.get('cost')), qp(batch.get('targetc')), count.data_ptr(),
                 C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))))
         n_valid = int(count.item())
         batch = {k: v[:n_valid] for k, v in batch.items()}

@@ -8,6 +8,10 @@ loop.  Per control step: one `gxl_policy_step` launch (libguardx_safelayer.so, i
 update of the step just made, ac.step, g_net, the correction) and one `gx_step_slab` launch on act_safe[t] (env.step with
 the speculated reset_done, committed on the host) -- the two launches per control step the step-wise rollout_policy
 already has.  Everything runs on torch's current stream; nothing synchronises.
+
+episode=True is the collection loop of `safelayer_one_episode` (safelayer_one_episode/safelayer.py:493-590): no
+reset_done, the rows sanitised, the first-done bookkeeping, prev_c = the step's cost whatever `done` says
+(guardx_safelayer_policy_step_episode and a plain env.step per control step; _closed_loop.run_episode).
 """
 import ctypes as C
 
@@ -72,7 +76,14 @@ class State(_cl.State):
         self.prev_c.zero_()    # safelayer.py:567
 
 
-def rollout(env, params, T, g_net, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0):
+def tail_probe(params, rows, act_dim, g_net):
+    """the tail of an episode=True call alone on `rows` (n, D) (guardx_safelayer_tail_probe): -> obs_last (raw), val_last"""
+    lib = _safelayer_native.load()
+    return _cl.tail_probe("tail_probe", params, rows, act_dim, g_net, lambda n, D, A: _cl.hidden_of(n, lambda h: g_floats(D, A, h)),
+                          lib.gxl_work_floats, lib.gxl_prepare, lib.guardx_safelayer_tail_probe, _safelayer_native.check)
+
+
+def rollout(env, params, T, g_net, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0, episode=False):
     obs0, N, D, A, T = _cl.begin(env, "rollout_safelayer", obs0, T)
     if g_net is None or not torch.is_tensor(g_net) or getattr(g_net, G_NET_ATTR, None) is None:
         raise ValueError("rollout_safelayer needs g_net=Engine.pack_g_net(ac.ccritic, device=...) (the declaration "
@@ -101,5 +112,7 @@ def rollout(env, params, T, g_net, obs0=None, noise_seed=(0, 0), correct=True, d
     def prepare(stream):
         return lib.gxl_prepare(D, A, hidden, g_hidden, a.d_params, a.d_g_params, a.d_work, stream)
 
+    if episode:
+        return _cl.run_episode(env, st, a, out, T, prepare, lib.guardx_safelayer_policy_step_episode, _safelayer_native.check, out['act_safe'])
     _cl.run(env, st, a, out, T, prepare, lib.gxl_policy_step, _safelayer_native.check, out['act_safe'])
     return out

@@ -70,8 +70,15 @@ def correction_probe(q_critic, obs, act, delta=0.0, niter=20, eta=0.05, grad_sca
 State = _cl.State
 
 
+def tail_probe(params, rows, act_dim, q_critic):
+    """the tail of an episode=True call alone on `rows` (n, D) (guardx_usl_tail_probe): -> obs_last (raw), val_last"""
+    lib = _usl_native.load()
+    return _cl.tail_probe("tail_probe", params, rows, act_dim, q_critic, _cl.q_hidden, lib.gxu_work_floats, lib.gxu_prepare,
+                          lib.guardx_usl_tail_probe, _usl_native.check)
+
+
 def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True, delta=0.0, niter=20, eta=0.05,
-            grad_scale=None):
+            grad_scale=None, episode=False):
     params, cp, obs0, N, D, A, T, hidden, c_hidden = _cl.q_rollout_inputs(env, "rollout_usl", params, q_critic, obs0, T)
     niter = int(niter)
     if niter < 0:
@@ -93,5 +100,7 @@ def rollout(env, params, T, q_critic, obs0=None, noise_seed=(0, 0), correct=True
     def prepare(stream):
         return lib.gxu_prepare(D, A, hidden, c_hidden, a.d_params, a.d_c_params, a.d_work, stream)
 
+    if episode:   # usl_one_episode/usl.py:454-554: no reset_done, the rows sanitised, the first-done bookkeeping
+        return _cl.run_episode(env, st, a, out, T, prepare, lib.guardx_usl_policy_step_episode, _usl_native.check, out['act_safe'])
     _cl.run(env, st, a, out, T, prepare, lib.gxu_policy_step, _usl_native.check, out['act_safe'])
     return out

@@ -145,6 +145,32 @@ gxe_status gxe_finish(int32_t N, int32_t T, int32_t D, int32_t A, float gamma, f
                       float* d_mu_c, float* d_logp_c, float* d_ret, float* d_adv, float* d_cost_ret, float* d_adc,
                       int32_t* d_n_valid, void* stream);
 
+/* (guardx_episode_finish_cols below carries the library's full name instead of its gxe_ prefix: the set of gxe_ symbols
+ * is the library's first ABI, which stays as it was.)
+ * One extra column of guardx_episode_finish_cols: d_src [T][N][width] time-major -> d_dst [.][width], the valid rows compacted
+ * env-major like every other output. */
+#define GXE_FINISH_MAX_COLS 4
+typedef struct gxe_finish_col {
+    const float* d_src;
+    float* d_dst;
+    int32_t width;            /* >= 1 */
+} gxe_finish_col;
+
+/* gxe_finish (same arguments, same arithmetic, same two launches) plus, in the gather launch:
+ *   n_cols (0 .. GXE_FINISH_MAX_COLS) extra columns `cols` (a HOST array, read before the call returns);
+ *   with d_qc, d_qcost [T][N] and d_targetc [.] (all given or all null), per valid row t of env e
+ *       targetc = qcost[t] + gamma * qc[t + 1]   one fp32 multiply, then one fp32 add, no fused multiply-add;
+ *       the product is taken as +0.0f at t + 1 == L (usl_one_episode/usl.py:105-107: qc counts as 0 there).
+ * The one-episode buffers of the safelayer, USL and LPG learners (safelayer_one_episode/safelayer.py:30-140,
+ * usl_one_episode/usl.py:22-144): act_safe, cost, prev_cost columns, or act_safe, cost and targetc. */
+gxe_status guardx_episode_finish_cols(int32_t N, int32_t T, int32_t D, int32_t A, float gamma, float lam, int32_t* d_first_done,
+                           const float* d_obs, const float* d_act, const float* d_mu, const float* d_logp,
+                           const float* d_rew, const float* d_val, const float* d_val_last, const float* d_cost,
+                           const float* d_vc, const float* d_vc_last, float* d_work, float* d_obs_c, float* d_act_c,
+                           float* d_mu_c, float* d_logp_c, float* d_ret, float* d_adv, float* d_cost_ret, float* d_adc,
+                           int32_t n_cols, const gxe_finish_col* cols, const float* d_qc, const float* d_qcost,
+                           float* d_targetc, int32_t* d_n_valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,46 @@ gxu_status gxu_prepare(int32_t D, int32_t A, int32_t hidden, int32_t c_hidden, c
  * N == 0 launches nothing. */
 gxu_status gxu_policy_step(const gxu_step_args* args, void* stream);
 
+/* The per-env bookkeeping of a one-episode rollout, the second argument of guardx_usl_policy_step_episode.  The
+ * same declaration stands in guardx_safelayer.h, guardx_usl.h and guardx_lpg.h under one guard (each library's build
+ * id covers its own header alone).  The prologue of step t > 0 of such a launch does, per env, after its copies
+ * of rew / cost / done [t-1] and in this order, with k = t_base + t:
+ *       first_done == 0 ?  ep_ret += rew, ep_cost += cost (fp32, one add each), ep_len = k
+ *       done > 0 and first_done == 0 ?  first_done = k
+ * which is include/guardx_episode.h's bookkeeping, operation for operation.  Device addresses, dense, [N]. */
+#ifndef GX_FIRST_DONE_STATE_DEFINED
+#define GX_FIRST_DONE_STATE_DEFINED
+typedef struct gx_first_done_state {
+    uint32_t struct_size;     /* sizeof(gx_first_done_state) */
+    int32_t t_base;           /* steps of the episode made before this call (>= 0) */
+    int32_t* d_first_done;    /* 1-based index of the first step with done, 0 = not finished */
+    int32_t* d_ep_len;        /* steps counted into ep_ret / ep_cost */
+    float* d_ep_ret;          /* reward summed up to and including the first done step */
+    float* d_ep_cost;         /* cost likewise */
+} gx_first_done_state;
+#endif
+
+/* The two entries below carry the library's full name instead of its gxu_ prefix: the set of gxu_ symbols is the
+ * library's first ABI, which stays as it was. */
+/* The one-episode form of gxu_policy_step (the `usl_one_episode` learner: no reset_done between the steps; the
+ * driver's env launch is a plain step and d_obs_rd is the env's plain observation).  Same arguments, same checks,
+ * plus the bookkeeping of gx_first_done_state below (null, t_base < 0, a wrong struct_size or a null pointer
+ * in it: GXU_ERR_ARG, nothing launched).  Against gxu_policy_step:
+ *   the row read has every NaN / +Inf / -Inf entry replaced by +0.0f; that row feeds every network and is what
+ *   obs[t] keeps;
+ *   the prologue of t > 0 runs the first-done bookkeeping after its copies (gx_first_done_state);
+ *   the tail writes obs_last raw and val_last = v on the sanitised row, 0 for a row with any non-finite entry.
+ *   The sanitised row is what c_net reads in every pass of the iteration; qc, the correction and iters are
+ *   those of gxu_policy_step.
+ */
+gxu_status guardx_usl_policy_step_episode(const gxu_step_args* args, const gx_first_done_state* book, void* stream);
+
+/* The tail launch of the one-episode form alone on n caller-supplied rows d_rows [n][D] (after gxu_prepare on the
+ * same networks): d_obs_last = the rows as they are, d_val_last by the tail's rule.  No state is touched. */
+gxu_status guardx_usl_tail_probe(int32_t n, int32_t D, int32_t A, int32_t hidden, int32_t c_hidden, const float* d_params,
+                          const float* d_c_params, const float* d_work, const float* d_rows, float* d_obs_last,
+                          float* d_val_last, void* stream);
+
 /* The iteration alone, with the step kernel's own device functions, on n caller-supplied rows d_obs [n][D], d_act
  * [n][A]:  d_a_safe [n][A] the final a;  d_q0 [n] Q at the input action;  d_grad0 [n][A] the scaled gradient s of the
  * first pass, 0 for a row that stops before it;  d_iters [n] (int32) the updates applied;  d_stop [n] (int32) why the
