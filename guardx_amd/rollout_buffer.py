@@ -147,12 +147,14 @@ def gae_rollout(rew, val, done, last_val=None, gamma=0.99, lam=0.95):
 
 def _gae_host(rew, val, done, gamma, lam):
     """gae_rollout + the per-env normalisation for HOST tensors, in plain torch: the same recursion the kernels run
-    (paths closed with 0 at every done step and at step T - 1).  Returns (adv normalised, env-major (N, T); ret (T, N))."""
+    (paths closed with 0 at every step with done == 1 and at step T - 1).  A path closes where done == 1 and nowhere
+    else, which is what the kernels read (gx_gae.hip) and what the buffers of the three learners this serves do
+    (np.where(done == 1): safelayer.py:109, usl.py:112, lpg.py:112).  Returns (adv normalised, env-major (N, T); ret (T, N))."""
     T, N = rew.shape
     adv, ret = torch.empty_like(rew), torch.empty_like(rew)
     a_next, r_next, v_next = torch.zeros(N), torch.zeros(N), torch.zeros(N)
     for t in range(T - 1, -1, -1):
-        live = 1.0 - (done[t] > 0).to(torch.float32) if t + 1 < T else torch.zeros(N)
+        live = 1.0 - (done[t] == 1).to(torch.float32) if t + 1 < T else torch.zeros(N)
         delta = rew[t] + gamma * live * v_next - val[t]
         a_next = delta + gamma * lam * live * a_next
         r_next = rew[t] + gamma * live * r_next
@@ -252,13 +254,14 @@ def safelayer_rollout_batch(out, gamma=0.99, lam=0.95):
 
 def _q_target_batch(out, gamma, lam, who, source):
     """USLBufferX.get() and LPGBufferX.get(): the two classes keep the same fields, close paths the same way and build
-    the same targetc (usl.py:26-159 and lpg.py:26-159 differ in their names only)"""
+    the same targetc (usl.py:26-159 and lpg.py:26-159 differ in their names only).  Both close a path where done == 1
+    (usl.py:112, lpg.py:112), so that is where qc[t + 1] is taken as 0, on host tensors as in the kernels."""
     _require(out, ('obs', 'act', 'act_safe', 'rew', 'val', 'logp', 'mu', 'logstd', 'cost', 'qc', 'done'), who, source)
     adv, ret = _channel(out['rew'], out['val'], out['done'], None, gamma, lam)
     f = lambda x: x.to(torch.float32)   # noqa: E731
     qc, done = f(out['qc']), f(out['done'])
     q_next = torch.zeros_like(qc)
-    q_next[:-1] = qc[1:] * (1.0 - (done[:-1] > 0).to(torch.float32))
+    q_next[:-1] = qc[1:] * (1.0 - (done[:-1] == 1).to(torch.float32))
     targetc = f(out['cost']) + float(gamma) * q_next
     return _batch(out, adv, ret, act_safe=out['act_safe'], cost=out['cost'], targetc=targetc)
 
