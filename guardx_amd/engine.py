@@ -332,6 +332,7 @@ class Engine:
         self._spec = C.c_int32(0)
         self._spec_ref = C.byref(self._spec)
         self._rd_obs = None          # what reset_done() returns for the step just made (speculated in-kernel)
+        self._rd_flushed = None      # the _rd_obs whose requested re-initialisation get_state() has installed
         self._statewise = None       # rollout_statewise's M / first / step counter (guardx_amd/statewise.py), made on first use
         self._safelayer = None       # rollout_safelayer's prev_c / step counter (guardx_amd/safelayer.py), made on first use
         self._usl = None             # rollout_usl's step counter and slab (guardx_amd/usl.py), made on first use
@@ -585,12 +586,13 @@ class Engine:
             # already evaluated by the step() launch: request the re-initialisation (installed by the next
             # launch on this engine) and hand out the observation -- no kernel of its own
             st = self._gx_commit(self._h)
-            if st:
+            if st and not (st == _native.GX_ERR_STATE and self._rd_flushed is self._rd_obs):
                 _native.check(st)
-            return self._rd_obs
+            return self._rd_obs      # (refused behind get_state(), which installed the request: nothing is left to ask for)
         out = self._new(self.env_num, self.obs_flat_size)
-        _native.check(self._lib.gx_reset_done(self._h, self._obs.data_ptr(), out.data_ptr(),
-                                              self._stream()))
+        # (after rollout(packed=True) _obs is a view of the packed rows, row stride D + A + 3: the kernel reads dense rows)
+        src = self._obs if self._obs.is_contiguous() else self._obs.contiguous()
+        _native.check(self._lib.gx_reset_done(self._h, src.data_ptr(), out.data_ptr(), self._stream()))
         return out
 
     def rollout(self, actions, packed=False):
@@ -1098,6 +1100,7 @@ class Engine:
                                              key, C.byref(hist)))
         s['key'] = np.array([key[0], key[1]], np.uint32)
         s['hist'] = int(hist.value)
+        self._rd_flushed = self._rd_obs      # a requested reset_done is part of the state: gx_get_state installed it
         return s
 
     def set_state(self, s):
