@@ -1,9 +1,10 @@
-"""What the closed-loop rollouts with a third network share (statewise.py, safelayer.py, usl.py, lpg.py; the
-one-episode form of the last three: Book, run_episode, tail_probe): the sizes of
-the packed networks, the checks of the inputs (for the two learners with a Q critic, usl.py and lpg.py, also those of
-their probes and the tensors their rollouts return), the common fields of a gx?_step_args, the loop itself -- per control step the
-path's policy-step launch and one `gx_step_slab` launch (env.step with the speculated reset_done, committed on the
-host) -- and what the loop leaves on the engine, which is what rollout_policy leaves.
+"""What the closed-loop rollouts share (Engine.rollout_policy and pack_actor_critic; statewise.py, safelayer.py, usl.py,
+lpg.py; episode.py and the one-episode form of safelayer, usl and lpg: Book, run_episode, tail_probe): the sizes of
+the packed networks, the checks of the networks and of the inputs (for the two learners with a Q critic, usl.py and
+lpg.py, also those of their probes and the tensors their rollouts return), the common fields of a gx?_step_args, the
+loop itself -- per control step the path's policy-step launch and one `gx_step_slab` launch (env.step with the
+speculated reset_done, committed on the host; a plain env.step in the one-episode form) -- and what the loop leaves on
+the engine, which is what rollout_policy leaves.
 """
 import ctypes as C
 
@@ -11,7 +12,7 @@ import torch
 
 from . import _native
 from ._sidelib import FirstDoneState
-from .critic import HIDDEN
+from .critic import HIDDEN, critic_floats, critic_hidden
 
 
 def net_floats(D, out, h):
@@ -126,9 +127,30 @@ def flatten(lin, device):
     return flat.to(device) if device is not None else flat
 
 
+def refuse_softplus(who, cost_critic):
+    """`who` evaluates its cost critic with a linear output (pack_critic's declaration travels with the tensor)"""
+    if getattr(cost_critic, 'gx_output', None) == 'softplus':
+        raise ValueError(f"{who} evaluates the cost critic with a linear output; cost_critic was packed with "
+                         "output='softplus' (SCPO's MLPMaxCostCritic: use rollout_statewise)")
+
+
+def linear_cost_critic(who, cost_critic, D, device):
+    """The cost critic of rollout_policy and rollout_episode: -> the packed critic as a contiguous float32 tensor on the
+    device and its hidden width, (None, None) without one"""
+    if cost_critic is None:
+        return None, None
+    refuse_softplus(who, cost_critic)
+    vcp = cost_critic.to(device=device, dtype=torch.float32).contiguous()
+    vc_hidden = critic_hidden(D, vcp.numel())
+    if vc_hidden is None:
+        raise ValueError(f"cost_critic has {vcp.numel()} floats; expected one of "
+                         f"{[critic_floats(D, h) for h in HIDDEN]} (hidden {HIDDEN})")
+    return vcp, vc_hidden
+
+
 class Book:
-    """the first-done bookkeeping of a path's one-episode form (episode=True): per env first_done / ep_len (int32),
-    ep_ret / ep_cost (float32), and the number of steps the episode has made (t_base)"""
+    """the first-done bookkeeping of a one-episode rollout (rollout_episode, episode=True): per env first_done / ep_len
+    (int32), ep_ret / ep_cost (float32), and the number of steps the episode has made (t_base)"""
 
     def __init__(self, env):
         N = env.env_num
@@ -151,8 +173,9 @@ class Book:
 
 class State:
     """what a path keeps per engine: the one-set output slab of its env.step launches, its own count of policy steps
-    (the noise counter: 0 at construction, + T per call, not reset by reset()) and, once an episode=True call was made,
-    that form's bookkeeping (`book`: advanced by episode=True calls of the path alone, cleared by Engine.reset())"""
+    (the noise counter: 0 at construction, + T per call, not reset by reset()) and, once a one-episode call was made,
+    that form's bookkeeping (`book`: advanced by one-episode calls of the path alone).  Engine.reset() calls reset(),
+    which a path with state of its own overrides, and reset_book()."""
     book = None
 
     def __init__(self, env):
@@ -167,22 +190,23 @@ class State:
             self.book.reset()
 
 
-def begin(env, name, obs0, T):
-    """-> obs0 (the engine's when None), N, D, A, T"""
+def begin(env, name, obs0, T, check_T=True):
+    """-> obs0 (the engine's when None), N, D, A, T; check_T=False leaves T < 1 to the library's own refusal"""
     if obs0 is None:
         obs0 = env._obs
     if obs0 is None:
         raise RuntimeError(f"{name}() before reset()")
     T = int(T)
-    if T < 1:
+    if check_T and T < 1:
         raise ValueError(f"{name}: T must be >= 1")
     return obs0, env.env_num, env.obs_flat_size, env.action_space.shape[0], T
 
 
 def device_inputs(env, params, third, obs0, Din, A, tail=""):
-    """params, the third network and obs0 as contiguous float32 tensors on the engine's device, and the policy's hidden
-    width, read off its size for Din inputs"""
-    params, third, obs0 = (t.to(device=env.device, dtype=torch.float32).contiguous() for t in (params, third, obs0))
+    """params, the third network (None where the path has none to move) and obs0 as contiguous float32 tensors on the
+    engine's device, and the policy's hidden width, read off its size for Din inputs"""
+    params, third, obs0 = (t if t is None else t.to(device=env.device, dtype=torch.float32).contiguous()
+                           for t in (params, third, obs0))
     N, D = env.env_num, env.obs_flat_size
     if tuple(obs0.shape) != (N, D):
         raise ValueError(f"obs0 has shape {tuple(obs0.shape)}; expected {(N, D)}")
@@ -247,11 +271,12 @@ def run(env, st, a, out, T, prepare, step_fn, check, act):
     return out
 
 
-def run_episode(env, st, a, out, T, prepare, step_fn, check, act):
-    """The one-episode form of run(): prepare(stream), then T x (step_fn(args, book) -> env.step(act[t])) and the closing
-    step_fn at t = T.  No reset_done: the env launch is a plain step (flags = 0, nothing speculated, nothing committed)
-    and the policy step reads the env's plain observation, set 0 of the slab, as guardx_amd/episode.py does.  Adds the
-    copies of the bookkeeping and t0 to `out`; the engine is left as after a step()."""
+def run_episode(env, st, a, out, T, prepare, step_fn, check, act, book_in_args=False):
+    """The one-episode form of run(): prepare(stream), then T x (step_fn -> env.step(act[t])) and the closing step_fn at
+    t = T.  No reset_done: the env launch is a plain step (flags = 0, nothing speculated, nothing committed) and the
+    policy step reads the env's plain observation, set 0 of the slab.  step_fn(args, book, stream) takes the path's
+    bookkeeping as a gx_first_done_state; book_in_args: step_fn(args, stream), and `a` has the same five fields itself
+    (gxe_step_args).  Adds the copies of the bookkeeping and t0 to `out`; the engine is left as after a step()."""
     book = st.book
     if book is None:
         book = st.book = Book(env)
@@ -259,7 +284,13 @@ def run_episode(env, st, a, out, T, prepare, step_fn, check, act):
     a.d_obs_rd = slab[0][0].data_ptr()     # a flags = 0 step writes no obs_rd piece
     b = book.c_struct()
     stream = env._raw_stream(env._dev_index)
-    h, ref, bref, spec_ref = env._h, C.byref(a), C.byref(b), env._spec_ref
+    h, ref, spec_ref = env._h, C.byref(a), env._spec_ref
+    if book_in_args:
+        for f in ('t_base', 'd_first_done', 'd_ep_len', 'd_ep_ret', 'd_ep_cost'):
+            setattr(a, f, getattr(b, f))
+        step_args = (ref, stream)
+    else:
+        step_args = (ref, C.byref(b), stream)
     slab_fn = env._gx_step_slab
     act_ptr, act_stride, slab_ptr = act.data_ptr(), 4 * act.shape[1] * act.shape[2], slab[6]
     env._rd_obs = None
@@ -267,14 +298,14 @@ def run_episode(env, st, a, out, T, prepare, step_fn, check, act):
         check(prepare(stream))
         for t in range(T):
             a.t = t
-            rc = step_fn(ref, bref, stream)
+            rc = step_fn(*step_args)
             if rc:
                 check(rc)
-            rc = slab_fn(h, act_ptr + t * act_stride, slab_ptr, 0, 0, spec_ref, stream)   # env.step(act_safe[t]), nothing else
+            rc = slab_fn(h, act_ptr + t * act_stride, slab_ptr, 0, 0, spec_ref, stream)   # env.step(act[t]), nothing else
             if rc:
                 _native.check(rc)
         a.t = T
-        check(step_fn(ref, bref, stream))
+        check(step_fn(*step_args))
     out['t0'] = book.t_base
     st.steps += T
     book.t_base += T
@@ -286,10 +317,12 @@ def run_episode(env, st, a, out, T, prepare, step_fn, check, act):
     return out
 
 
-def tail_probe(name, params, rows, act_dim, third, third_hidden, work_floats, prepare_fn, probe_fn, check):
-    """The tail of an episode=True call alone on `rows` (n, D), a float32 device tensor, through a library's
-    guardx_<library>_tail_probe: -> obs_last (the rows as they are) and val_last (the critic on the sanitised rows, 0 for a row with a
-    non-finite entry).  third: the packed third network on the rows' device; third_hidden(D, A) its hidden width or None."""
+def tail_probe(name, params, rows, act_dim, third, third_hidden, work_floats, prepare_fn, probe_fn, check, vc_last=False):
+    """The tail of a one-episode call alone on `rows` (n, D), a float32 device tensor, through a library's tail probe:
+    -> obs_last (the rows as they are) and val_last (the critic on the sanitised rows, 0 for a row with a non-finite
+    entry).  third: the packed third network; third_hidden(floats, D, A) its hidden width or None.  vc_last: the third
+    network is a cost critic that may be absent (None: the value network's block of `params` stands in) and whose values
+    on the rows the probe returns as vc_last (gxe_tail_probe: has_vc after the widths, d_vc_last after d_val_last)."""
     if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2):
         raise ValueError(f"{name}: rows must be a float32 (n, D) device tensor")
     rows = rows.contiguous()
@@ -298,18 +331,27 @@ def tail_probe(name, params, rows, act_dim, third, third_hidden, work_floats, pr
     if n >= 2 ** 31:
         raise ValueError(f"{name}: more than 2^31 - 1 rows")
     params = params.to(device=rows.device, dtype=torch.float32).contiguous()
-    third = third.to(device=rows.device, dtype=torch.float32).contiguous()
+    absent = vc_last and third is None      # only gxe_tail_probe's cost critic may be
+    if not absent:
+        third = third.to(device=rows.device, dtype=torch.float32).contiguous()
     hidden = hidden_of(params.numel(), lambda h: policy_floats(D, A, h))
-    h3 = third_hidden(third.numel(), D, A)
+    h3 = hidden if absent else third_hidden(third.numel(), D, A)
     if hidden is None or h3 is None:
-        raise ValueError(f"{name}: {'params' if hidden is None else 'the third network'} does not fit {D} inputs, {A} "
-                         f"actions and a hidden width of {HIDDEN}")
+        raise ValueError(f"{name}: {'params' if hidden is None else 'cost_critic' if vc_last else 'the third network'} "
+                         f"does not fit {D} inputs, {A} actions and a hidden width of {HIDDEN}")
+    if absent:
+        third = params[net_floats(D, A, hidden):]
     new = lambda *s: torch.empty(s, dtype=torch.float32, device=rows.device)   # noqa: E731
     out = dict(obs_last=new(n, D), val_last=new(n))
+    flag, vc_ptr = (), ()
+    if vc_last:
+        if not absent:
+            out['vc_last'] = new(n)
+        flag, vc_ptr = (int(not absent),), (None if absent else out['vc_last'].data_ptr(),)
     work = new(int(work_floats(D, A, hidden, h3)))
     stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(rows.device.index))
     with torch.cuda.device(rows.device):
         check(prepare_fn(D, A, hidden, h3, params.data_ptr(), third.data_ptr(), work.data_ptr(), stream))
-        check(probe_fn(n, D, A, hidden, h3, params.data_ptr(), third.data_ptr(), work.data_ptr(), rows.data_ptr(),
-                       out['obs_last'].data_ptr(), out['val_last'].data_ptr(), stream))
+        check(probe_fn(n, D, A, hidden, h3, *flag, params.data_ptr(), third.data_ptr(), work.data_ptr(), rows.data_ptr(),
+                       out['obs_last'].data_ptr(), out['val_last'].data_ptr(), *vc_ptr, stream))
     return out

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import _native
+from . import _closed_loop as _cl, _native, critic as _critic
 from .spaces import Box
 
 __all__ = ["Engine", "ResamplingError"]
@@ -337,7 +337,7 @@ class Engine:
         self._safelayer = None       # rollout_safelayer's prev_c / step counter (guardx_amd/safelayer.py), made on first use
         self._usl = None             # rollout_usl's step counter and slab (guardx_amd/usl.py), made on first use
         self._lpg = None             # rollout_lpg's q_init / step counter and slab (guardx_amd/lpg.py), made on first use
-        self._episode = None         # rollout_episode's first_done / sums / step counter (guardx_amd/episode.py), made on first use
+        self._episode = None         # rollout_episode's bookkeeping / step counter and slab (guardx_amd/episode.py), made on first use
         self._obs = None
         self._reward = None
         self._done = None
@@ -484,15 +484,10 @@ class Engine:
         obs = self._new(self.env_num, self.obs_flat_size)
         _native.check(self._lib.gx_reset(self._h, obs.data_ptr(), self._stream()))
         self._rd_obs = None
-        if self._statewise is not None:
-            self._statewise.reset()     # M = 0, first = 1 (scpo.py:637-639, 697-699)
-        if self._safelayer is not None:
-            self._safelayer.reset()     # prev_c = 0 (safelayer.py:507, 567)
-        if self._episode is not None:
-            self._episode.reset()       # first_done = ep_ret = ep_cost = ep_len = 0, the episode starts over
-        for st in (self._safelayer, self._usl, self._lpg):
+        for st in (self._statewise, self._safelayer, self._usl, self._lpg, self._episode):
             if st is not None:
-                st.reset_book()         # the same for the episode=True form of the three safe-action rollouts
+                st.reset()              # the path's own: M = 0, first = 1 (scpo.py:637-639, 697-699); prev_c = 0 (safelayer.py:507, 567)
+                st.reset_book()         # first_done = ep_ret = ep_cost = ep_len = 0: the one-episode forms start over
         if not check:
             self._obs = obs
             return obs
@@ -783,7 +778,8 @@ class Engine:
     # ------------------------------------------------------------------
     # closed-loop fused rollout (policy evaluated inside the kernel)
     # ------------------------------------------------------------------
-    POLICY_HIDDEN = (64, 128, 192, 256)
+    POLICY_HIDDEN = _critic.HIDDEN
+    _policy_floats = staticmethod(_cl.policy_floats)
 
     @staticmethod
     def pack_actor_critic(ac=None, *, mu_net=None, v_net=None, log_std=None, device=None):
@@ -794,37 +790,19 @@ class Engine:
         input width that does not match) raises NotImplementedError."""
         if ac is not None:
             mu_net, v_net, log_std = ac.pi.mu_net, ac.v.v_net, ac.pi.log_std
-        parts, widths, lins = [], set(), []
-        for net in (mu_net, v_net):
-            mods = [m for m in net if not isinstance(m, torch.nn.Identity)]
-            lin = [m for m in mods if isinstance(m, torch.nn.Linear)]
-            if len(lin) != 3 or lin[0].out_features != lin[1].out_features or lin[1].in_features != lin[0].out_features \
-                    or lin[2].in_features != lin[1].out_features:
-                raise NotImplementedError("rollout_policy supports two hidden layers of equal width (--l 2)")
-            if [type(m) for m in mods] != [torch.nn.Linear, torch.nn.Tanh] * 2 + [torch.nn.Linear]:
-                raise NotImplementedError("rollout_policy supports Tanh hidden activations and a linear output only "
-                                          "(activation=nn.Tanh, output_activation=nn.Identity)")
-            widths.add(lin[0].out_features)
-            lins.append(lin)
-            for m in lin:
-                parts += [m.weight.detach().reshape(-1), m.bias.detach().reshape(-1)]
-        if len(widths) != 1 or widths.pop() not in Engine.POLICY_HIDDEN:
-            raise NotImplementedError(f"rollout_policy supports hidden_sizes (h, h) with h in {Engine.POLICY_HIDDEN}, "
-                                      "the same for actor and critic")
-        if lins[0][0].in_features != lins[1][0].in_features:
+        pi, v = (_cl.two_tanh_layers([m for m in net if not isinstance(m, torch.nn.Identity)], "rollout_policy", tanh_tail=(
+            " and a linear output only (activation=nn.Tanh, output_activation=nn.Identity)")) for net in (mu_net, v_net))
+        if pi[0].out_features != v[0].out_features:
+            raise NotImplementedError("rollout_policy supports hidden_sizes (h, h), the same for actor and critic")
+        if pi[0].in_features != v[0].in_features:
             raise NotImplementedError("rollout_policy needs the actor and the critic to read the same observation width")
-        if lins[1][2].out_features != 1:
+        if v[2].out_features != 1:
             raise NotImplementedError("rollout_policy supports a critic with one output")
         log_std = torch.as_tensor(log_std).detach().reshape(-1)
-        if log_std.numel() != lins[0][2].out_features:
-            raise NotImplementedError(f"log_std has {log_std.numel()} entries, mu_net {lins[0][2].out_features} outputs")
-        parts.append(log_std)
-        flat = torch.cat([t.to(torch.float32) for t in parts])
+        if log_std.numel() != pi[2].out_features:
+            raise NotImplementedError(f"log_std has {log_std.numel()} entries, mu_net {pi[2].out_features} outputs")
+        flat = torch.cat([_cl.flatten(pi, None), _cl.flatten(v, None), log_std.to(torch.float32)])
         return flat.to(device) if device is not None else flat
-
-    @staticmethod
-    def _policy_floats(D, A, h):
-        return 2 * (h * D + h + h * h + h) + (A + 1) * h + (A + 1) + A
 
     @staticmethod
     def pack_critic(critic, device=None, *, output='identity'):
@@ -834,7 +812,7 @@ class Engine:
         output='softplus': SCPO's MLPMaxCostCritic (scpo_core.py:158-166), the same layers followed by nn.Softplus
         (beta 1, threshold 20), for rollout_statewise(..., cost_critic=).  The layout is the same; the returned tensor
         carries the declaration (guardx_amd.statewise.critic_output), and each rollout refuses the other kind."""
-        from . import _closed_loop as _cl, statewise as _sw
+        from . import statewise as _sw
         if output not in ('identity', 'softplus'):
             raise ValueError(f"pack_critic: output must be 'identity' or 'softplus', got {output!r}")
         net = getattr(critic, 'v_net', critic)
@@ -998,27 +976,11 @@ class Engine:
         cost_critic = pack_critic(ac.vc) (CPO-family learners, cpo.py:600): the dict also holds vc (T,N) = Vc(obs[t])
         and vc_last (N,) = Vc(obs_last), from one batched pass over the recorded observations right after the rollout,
         on the same stream (guardx_amd.critic), with the bits of the value head; its width may differ from the actor's."""
-        if obs0 is None:
-            obs0 = self._obs
-        if obs0 is None:
-            raise RuntimeError("rollout_policy() before reset()")
-        N, D, A, T = self.env_num, self.obs_flat_size, self.action_space.shape[0], int(T)
-        params = params.to(device=self.device, dtype=torch.float32).contiguous()
-        obs0 = obs0.to(device=self.device, dtype=torch.float32).contiguous()
-        assert tuple(obs0.shape) == (N, D)
-        hidden = next((h for h in self.POLICY_HIDDEN if self._policy_floats(D, A, h) == params.numel()), None)
-        if hidden is None:
-            raise ValueError(f"params has {params.numel()} floats; expected one of "
-                             f"{[self._policy_floats(D, A, h) for h in self.POLICY_HIDDEN]} (hidden {self.POLICY_HIDDEN})")
+        obs0, N, D, A, T = _cl.begin(self, "rollout_policy", obs0, T, check_T=False)
+        assert tuple(obs0.shape) == (N, D)      # (an AssertionError here, where the later paths raise ValueError)
+        params, _, obs0, hidden = _cl.device_inputs(self, params, None, obs0, D, A)
+        cost_critic, _ = _cl.linear_cost_critic("rollout_policy", cost_critic, D, self.device)
         if cost_critic is not None:
-            from . import critic as _critic
-            if getattr(cost_critic, 'gx_output', None) == 'softplus':
-                raise ValueError("rollout_policy evaluates the cost critic with a linear output; cost_critic was packed "
-                                 "with output='softplus' (SCPO's MLPMaxCostCritic: use rollout_statewise)")
-            cost_critic = cost_critic.to(device=self.device, dtype=torch.float32).contiguous()
-            if _critic.critic_hidden(D, cost_critic.numel()) is None:
-                raise ValueError(f"cost_critic has {cost_critic.numel()} floats; expected one of "
-                                 f"{[_critic.critic_floats(D, h) for h in _critic.HIDDEN]} (hidden {_critic.HIDDEN})")
             _critic._critic_native.load()     # a missing critic library fails here, before anything is launched
         self._rd_obs = None
         out = dict(obs=self._new(T, N, D), act=self._new(T, N, A), logp=self._new(T, N), val=self._new(T, N),

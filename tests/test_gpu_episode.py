@@ -208,14 +208,14 @@ def test_bookkeeping_across_calls_reset_and_other_paths(main_run):
     _assert_state(gb, tuple(g[k] for k in ('first_done', 'ep_ret', 'ep_cost', 'ep_len')), "two halves")
     # other paths neither read nor write the state
     st = E._episode
-    before = (st.ints.clone(), st.sums.clone(), st.t_base, st.steps)
+    before = (st.book.ints.clone(), st.book.sums.clone(), st.book.t_base, st.steps)
     E.step(torch.zeros(N, 2, device='cuda'))
     E.reset_done()
     E.rollout_policy(p, 3, noise_seed=SEED)
-    assert torch.equal(st.ints, before[0]) and torch.equal(st.sums, before[1]) and (st.t_base, st.steps) == before[2:]
+    assert torch.equal(st.book.ints, before[0]) and torch.equal(st.book.sums, before[1]) and (st.book.t_base, st.steps) == before[2:]
     assert (before[0][0] > 0).any()
     E.reset()
-    assert int(st.ints.abs().sum()) == 0 and float(st.sums.abs().sum()) == 0 and st.t_base == 0
+    assert int(st.book.ints.abs().sum()) == 0 and float(st.book.sums.abs().sum()) == 0 and st.book.t_base == 0
     assert st.steps == T                                         # the noise counter is not reset
     c = E.rollout_episode(p, 2, noise_seed=SEED)
     assert c['t0'] == 0 and 'vc' not in c

@@ -317,7 +317,7 @@ def test_bookkeeping_across_calls_reset_and_other_paths(runs, learner):
     E.reset_done()
     E.rollout_episode(p, 2, noise_seed=SEED)
     assert torch.equal(book.ints, before[0]) and torch.equal(book.sums, before[1]) and book.t_base == before[2]
-    assert E._episode.t_base == 2 and st.steps == T + 3          # each path its own counters
+    assert E._episode.book.t_base == 2 and st.steps == T + 3          # each path its own counters
     E.reset()
     assert int(book.ints.abs().sum()) == 0 and float(book.sums.abs().sum()) == 0 and book.t_base == 0
     assert st.steps == T + 3                                     # the noise counter is not reset

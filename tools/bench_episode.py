@@ -70,7 +70,7 @@ def main():
 
                 def episode():
                     if Ee._episode is not None:
-                        Ee._episode.reset()          # a new episode for the bookkeeping; the envs go on (num_steps = 1000)
+                        Ee._episode.reset_book()     # a new episode for the bookkeeping; the envs go on (num_steps = 1000)
                     return episode_rollout_batch(Ee.rollout_episode(p, T, cost_critic=vcp), gamma, lam)
 
                 def stepwise():
