@@ -1,5 +1,6 @@
 """Build libguardx_hip.so and the side libraries of LIBRARIES (libguardx_critic.so, libguardx_statewise.so,
-libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so, libguardx_episode.so) for gfx950 in-tree with hipcc.
+libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so, libguardx_episode.so, libguardx_mathprobe.so) for gfx950
+in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -64,7 +65,8 @@ BUILD_ID_FILE = os.path.join(LIB_DIR, "BUILD_ID")
 LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
 
 # The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer, the USL, the LPG and the
-# one-episode policy step.
+# one-episode policy step; and the math probe, which only the tests call (the fp32 primitives of gx_device.h and
+# gx_policy.h one by one, tests/test_gpu_math64.py).
 # Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
 # libguardx_hip.so -- and the profiles taken on that build -- alone.
 _SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
@@ -116,6 +118,7 @@ LIBRARIES = {lib.key: lib for lib in (
     SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _Q_HEADERS),
     SideLibrary("lpg", "GXP_BUILD_ID", ["gx_lpg.hip"], _Q_HEADERS),
     SideLibrary("episode", "GXE_BUILD_ID", ["gx_episode.hip"], _STEP_HEADERS),
+    SideLibrary("mathprobe", "GXM_BUILD_ID", ["gx_mathprobe.hip"], _SIDE_HEADERS),
 )}
 
 
@@ -186,7 +189,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All seven libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All eight libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)

@@ -1,6 +1,7 @@
 """The C header of a side library (include/guardx_<key>.h, prefix gx?_) parsed into ctypes prototypes, and the
 comparison of the library's binding (guardx_amd/_<key>_native.py) with it: shared by the host suites of the statewise,
-the safelayer, the usl and the lpg library."""
+the safelayer, the usl and the lpg library; prototypes() also by those of the episode and the mathprobe library (the
+latter has no step_args: tests/test_native_abi.py)."""
 import ctypes as C
 import os
 import re
@@ -16,7 +17,9 @@ def header(key):
 def _ctype(decl, prefix, step_args):
     base = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, prefix + "_status": C.c_int,
             "float": C.c_float, "const char*": C.c_char_p, "void*": C.c_void_p, "const float*": C.c_void_p,
-            "float*": C.c_void_p, "int32_t*": C.c_void_p}
+            "float*": C.c_void_p, "int32_t*": C.c_void_p,
+            # the mathprobe library's: counters, a 64-bit count, its report (a device address like every d_ argument)
+            "uint64_t": C.c_uint64, "const uint32_t*": C.c_void_p, prefix + "_sweep_report*": C.c_void_p}
     t = re.sub(r"\s+", " ", decl.strip())
     t = re.sub(r"\s*\*\s*", "* ", t).strip()
     t = re.sub(r"\s+[A-Za-z_][A-Za-z_0-9]*$", "", t) if not t.endswith("*") and " " in t else t

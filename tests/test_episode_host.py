@@ -21,7 +21,7 @@ N_SYMBOLS = 10
 def test_episode_source_hash_covers_its_sources():
     from guardx_amd import build
     libs = build.LIBRARIES
-    assert list(libs) == ["critic", "statewise", "safelayer", "usl", "lpg", "episode"]
+    assert list(libs) == ["critic", "statewise", "safelayer", "usl", "lpg", "episode", "mathprobe"]
     ep = libs["episode"]
     assert ep.sources == ["gx_episode.hip"] and ep.macro == "GXE_BUILD_ID"
     incs = [i for f in ("gx_episode.hip", "gx_step.h")
@@ -37,7 +37,7 @@ def test_episode_source_hash_covers_its_sources():
     recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
     assert build.source_hash() == recorded
     ids = {l.source_hash() for l in libs.values()} | {build.source_hash()}
-    assert len(ids) == 7 and len(ep.source_hash()) == 24
+    assert len(ids) == 8 and len(ep.source_hash()) == 24      # (the eighth: the tests' math probe, younger than this one)
     # the critic library's file list is what it was: the step core is not part of it
     assert libs["critic"].sources == ["gx_critic.hip"]
     assert libs["critic"].headers == ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_critic.h")]
