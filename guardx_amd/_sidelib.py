@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the side libraries (guardx_amd/build.py:LIBRARIES) share: load(), check() and the error
+"""What the ctypes bindings of the side libraries (guardx_amd/build.py:LIBRARIES and POST_LIBRARIES) share: load(), check() and the error
 class.  Like _native, there is no CPU fallback: a missing library is built in place with hipcc, and a library built from
 other sources than the tree's is refused.
 """
@@ -15,11 +15,12 @@ class FirstDoneState(C.Structure):
 
 
 class Binding:
-    """load / check / Error of LIBRARIES[key].  `prefix`: that of its C symbols ("gxu"); `symbols`: name -> (restype,
+    """load / check / Error of LIBRARIES[key] (or POST_LIBRARIES[key]).  `prefix`: that of its C symbols ("gxu"); `symbols`: name -> (restype,
     argtypes); `ok`: its OK status; `label`: its name in the error text ("usl")."""
 
     def __init__(self, key, prefix, symbols, ok, label):
-        self.side, self.prefix, self.symbols, self.ok = _build.LIBRARIES[key], prefix, symbols, ok
+        side = _build.LIBRARIES[key] if key in _build.LIBRARIES else _build.POST_LIBRARIES[key]
+        self.side, self.prefix, self.symbols, self.ok = side, prefix, symbols, ok
         self.path = self.side.lib
         self._lib = None
 

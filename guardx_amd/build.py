@@ -1,6 +1,6 @@
 """Build libguardx_hip.so and the side libraries of LIBRARIES (libguardx_critic.so, libguardx_statewise.so,
-libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so, libguardx_episode.so, libguardx_mathprobe.so) for gfx950
-in-tree with hipcc.
+libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so, libguardx_episode.so, libguardx_mathprobe.so) and those of POST_LIBRARIES
+(libguardx_epstats.so) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -120,6 +120,12 @@ LIBRARIES = {lib.key: lib for lib in (
     SideLibrary("episode", "GXE_BUILD_ID", ["gx_episode.hip"], _STEP_HEADERS),
     SideLibrary("mathprobe", "GXM_BUILD_ID", ["gx_mathprobe.hip"], _SIDE_HEADERS),
 )}
+# The libraries that work on what the rollouts return: a registry of its own, built after LIBRARIES under the same lock
+# with the same flags, so that the identities of everything above stand.  epstats (the learners' EpRet / EpCost / EpLen
+# bookkeeping, guardx_amd/epstats.py) includes none of the project's device headers.
+POST_LIBRARIES = {lib.key: lib for lib in (
+    SideLibrary("epstats", "GXT_BUILD_ID", ["gx_epstats.hip"], []),
+)}
 
 
 _COMPILER = None
@@ -189,7 +195,7 @@ def _dep_hash(src):
 
 def build(force=False, verbose=False, jobs=None):
     """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All eight libraries; returns the path of
+    and rename into place (nobody can dlopen a half-written file).  All nine libraries; returns the path of
     libguardx_hip.so."""
     import fcntl
     os.makedirs(OBJ_DIR, exist_ok=True)
@@ -198,7 +204,7 @@ def build(force=False, verbose=False, jobs=None):
         try:
             if force or needs_build():
                 _build_locked(force, verbose, jobs)
-            for side in LIBRARIES.values():
+            for side in list(LIBRARIES.values()) + list(POST_LIBRARIES.values()):
                 if force or side.needs_build():
                     _build_side_locked(side, verbose)
             return LIB
@@ -263,5 +269,5 @@ def _build_side_locked(side, verbose):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in LIBRARIES.values():
+    for side in list(LIBRARIES.values()) + list(POST_LIBRARIES.values()):
         print(side.key, "build id", side.built_id())

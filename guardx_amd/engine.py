@@ -966,6 +966,14 @@ class Engine:
         from . import episode as _ep
         return _ep.rollout(self, params, T, obs0, noise_seed, cost_critic)
 
+    @staticmethod
+    def episode_stats(out_or_rew, cost=None, done=None, **kw):
+        """What the learners log per epoch as EpRet / EpCost / EpLen / EpCostRet / MaxEpLenRet / VVals, and read back as
+        the constraint value of the CPO family, from a rollout's (T, N) rew / cost / done: guardx_amd.epstats.episode_stats
+        (one call on the device, no host synchronisation)."""
+        from . import epstats as _es
+        return _es.episode_stats(out_or_rew, cost, done, **kw)
+
     def rollout_policy(self, params, T, obs0=None, noise_seed=(0, 0), *, cost_critic=None):
         """T x (ac.step -> env.step -> reset_done) on device (trpo.py:466-547 with the actor-critic of
         trpo_core.py:110-173 evaluated there).  `params` = pack_actor_critic(ac); the hidden width is read off its
