@@ -6,8 +6,9 @@ module raises, and every Engine call goes through the C ABI below.
 import ctypes as C
 import os
 
+from . import _sidelib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libguardx_hip.so")
 
 GX_OK, GX_ERR_ARG, GX_ERR_UNSUPPORTED, GX_ERR_LAYOUT, GX_ERR_HIP, GX_ERR_STATE = range(6)
 
@@ -100,47 +101,15 @@ SYMBOLS = {
     "gx_split_probe": (C.c_int, [_U32P, C.c_int32, _FP, C.c_void_p]),
 }
 
-_lib = None
 
-
-def load():
-    """Load the HIP library; raises (never falls back) when it is unavailable or was built from other sources.
-
-    The library carries the hash of the sources it was built from (gx_build_id).  If the file is missing or the
-    hash on disk differs from the sources in the tree it is rebuilt in place with hipcc (one process at a time:
-    guardx_amd.build takes a file lock and renames the finished file into place); a library whose embedded id does
-    not match after that is refused."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    from . import build as _build
-    want = _build.source_hash()
-    if _build.needs_build():
-        try:
-            _build.build(force=False)
-        except Exception as exc:  # noqa: BLE001
-            raise ImportError(
-                f"{LIB_PATH} is missing or stale (sources {want}, library {_build.built_id()}) and could not be "
-                f"built with hipcc ({exc}); run `python -m guardx_amd.build` (guardx_amd has no CPU fallback)") from exc
-    path = LIB_PATH
+def _experiment_path():
+    """A/B experiments only (tools/build_variant.py): a variant built from the SAME sources with other flags"""
     if os.environ.get("GX_LIB") and os.environ.get("GX_LIB_EXPERIMENT") == "1":
-        # A/B experiments only (tools/build_variant.py): a variant built from the SAME sources with other flags
         path = os.path.abspath(os.environ["GX_LIB"])
         import warnings
         warnings.warn(f"guardx_amd: loading the EXPERIMENTAL library {path} (GX_LIB + GX_LIB_EXPERIMENT=1); its build id is not "
-                      "checked against the tree", RuntimeWarning, stacklevel=3)
-    lib = C.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the ABI drifted
-        fn.restype = res
-        fn.argtypes = args
-    got = lib.gx_build_id().decode()
-    if got != want and path == LIB_PATH:
-        raise ImportError(f"{LIB_PATH} was built from other sources (library {got}, tree {want}); "
-                          "run `python -m guardx_amd.build`")
-    _warn_if_unprofiled_compiler(lib)
-    _lib = lib
-    return lib
+                      "checked against the tree", RuntimeWarning, stacklevel=4)
+        return path
 
 
 def _warn_if_unprofiled_compiler(lib):
@@ -160,16 +129,9 @@ def _warn_if_unprofiled_compiler(lib):
     if len(lines) > 1 and lines[1].strip() and have != "unknown" and lines[1].strip() != have:
         warnings.warn(f"libguardx_hip.so was built with [{have}]; the parity soak and profiles of {os.path.basename(ids[-1])} "
                       f"were taken with [{lines[1].strip()}]: run `pytest -m gpu` and tests/soak_parity.py on this build",
-                      RuntimeWarning, stacklevel=3)
+                      RuntimeWarning, stacklevel=4)
 
 
-class GxError(RuntimeError):
-    def __init__(self, status, msg):
-        super().__init__(f"guardx status {status}: {msg}")
-        self.status = status
-
-
-def check(status):
-    if status != GX_OK:
-        msg = load().gx_last_error()
-        raise GxError(status, msg.decode() if msg else "")
+# load / check / GxError: guardx_amd/_sidelib.py, like the other eight libraries
+_side = _sidelib.Binding("hip", "gx", SYMBOLS, GX_OK, None, other_path=_experiment_path, loaded=_warn_if_unprofiled_compiler)
+LIB_PATH, load, check, GxError = _side.path, _side.load, _side.check, _side.Error

@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the side libraries (guardx_amd/build.py:LIBRARIES and POST_LIBRARIES) share: load(), check() and the error
-class.  Like _native, there is no CPU fallback: a missing library is built in place with hipcc, and a library built from
+"""What the ctypes bindings of the nine libraries (guardx_amd/build.py: MAIN and LIBRARIES) share: load(), check() and
+the error class.  There is no CPU fallback: a missing library is built in place with hipcc, and a library built from
 other sources than the tree's is refused.
 """
 import ctypes as C
@@ -15,49 +15,63 @@ class FirstDoneState(C.Structure):
 
 
 class Binding:
-    """load / check / Error of LIBRARIES[key] (or POST_LIBRARIES[key]).  `prefix`: that of its C symbols ("gxu"); `symbols`: name -> (restype,
-    argtypes); `ok`: its OK status; `label`: its name in the error text ("usl")."""
+    """load / check / Error of one library of guardx_amd/build.py.  `key`: its key there; `prefix`: that of its C
+    symbols ("gxu"); `symbols`: name -> (restype, argtypes); `ok`: its OK status; `label`: its name in the error text
+    ("usl", None for the main library).  Two hooks, for the main library: `other_path()` may name another file to load,
+    whose build id is then not checked; `loaded(lib)` runs once on the library that passed."""
 
-    def __init__(self, key, prefix, symbols, ok, label):
-        side = _build.LIBRARIES[key] if key in _build.LIBRARIES else _build.POST_LIBRARIES[key]
-        self.side, self.prefix, self.symbols, self.ok = side, prefix, symbols, ok
+    def __init__(self, key, prefix, symbols, ok, label, other_path=None, loaded=None):
+        self.side = _build.MAIN if key == _build.MAIN.key else _build.LIBRARIES[key]
+        self.prefix, self.symbols, self.ok = prefix, symbols, ok
         self.path = self.side.lib
+        self.other_path, self.loaded = other_path, loaded
         self._lib = None
+        where = f"guardx {label} status" if label else "guardx status"
 
         class Error(RuntimeError):
             def __init__(self, status, msg):
-                super().__init__(f"guardx {label} status {status}: {msg}")
+                super().__init__(f"{where} {status}: {msg}")
                 self.status = status
 
         Error.__name__ = Error.__qualname__ = prefix.capitalize() + "Error"
         self.Error = Error
 
+        def check(status):   # a closure: when the status is OK a call costs one comparison
+            if status != ok:
+                msg = getattr(self.load(), prefix + "_last_error")()
+                raise Error(status, msg.decode() if msg else "")
+
+        self.check = check
+
     def load(self):
-        """Load the library; raises (never falls back) when it is unavailable or was built from other sources."""
+        """Load the library; raises (never falls back) when it is unavailable or was built from other sources.
+
+        The library carries the hash of the sources it was built from (gx?_build_id).  If the file is missing or the
+        hash on disk differs from the sources in the tree it is rebuilt in place with hipcc (one process at a time:
+        guardx_amd.build takes a file lock and renames the finished file into place); a library whose embedded id does
+        not match after that is refused."""
         if self._lib is not None:
             return self._lib
-        side, path = self.side, self.path
+        side = self.side
         want = side.source_hash()
         if side.needs_build():
             try:
                 _build.build(force=False)
             except Exception as exc:  # noqa: BLE001
                 raise ImportError(
-                    f"{path} is missing or stale (sources {want}, library {side.built_id()}) and could not "
-                    f"be built with hipcc ({exc}); run `python -m guardx_amd.build`") from exc
+                    f"{self.path} is missing or stale (sources {want}, library {side.built_id()}) and could not be "
+                    f"built with hipcc ({exc}); run `python -m guardx_amd.build` (guardx_amd has no CPU fallback)") from exc
+        path = self.other_path and self.other_path() or self.path
         lib = C.CDLL(path)
         for name, (res, args) in self.symbols.items():
             fn = getattr(lib, name)  # AttributeError if the ABI drifted
             fn.restype = res
             fn.argtypes = args
         got = getattr(lib, self.prefix + "_build_id")().decode()
-        if got != want:
+        if got != want and path == self.path:
             raise ImportError(f"{path} was built from other sources (library {got}, tree {want}); "
                               "run `python -m guardx_amd.build`")
+        if self.loaded:
+            self.loaded(lib)
         self._lib = lib
         return lib
-
-    def check(self, status):
-        if status != self.ok:
-            msg = getattr(self.load(), self.prefix + "_last_error")()
-            raise self.Error(status, msg.decode() if msg else "")

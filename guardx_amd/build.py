@@ -1,6 +1,5 @@
-"""Build libguardx_hip.so and the side libraries of LIBRARIES (libguardx_critic.so, libguardx_statewise.so,
-libguardx_safelayer.so, libguardx_usl.so, libguardx_lpg.so, libguardx_episode.so, libguardx_mathprobe.so) and those of POST_LIBRARIES
-(libguardx_epstats.so) for gfx950 in-tree with hipcc.
+"""Build the project's shared libraries (MAIN, then every entry of LIBRARIES, in that order) for gfx950 in-tree with
+hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -16,8 +15,6 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
-OBJ_DIR = os.path.join(LIB_DIR, "obj")
-LIB = os.path.join(LIB_DIR, "libguardx_hip.so")
 # one translation unit per robot (gx_robot_kernels.inl instantiated for it), compiled in parallel
 SOURCES = ["gx_api.hip", "gx_kernels.hip", "gx_gae.hip", "gx_policy_step.hip", "gx_kernels_point.hip", "gx_kernels_point_bare.hip", "gx_kernels_swimmer.hip",
            "gx_kernels_point_split.hip", "gx_kernels_point_bare_split.hip", "gx_kernels_swimmer_split.hip",
@@ -51,82 +48,7 @@ _MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # is 3 % SLOWER without it (87.0 -> 89.3 us).
 PER_SOURCE_FLAGS = {"gx_kernels_point_split.hip": _MAX_ILP, "gx_kernels_point_bare_split.hip": _MAX_ILP,
                     "gx_kernels_swimmer_split.hip": _MAX_ILP, "gx_kernels_ant.hip": ["-fno-slp-vectorize"]}
-
-
-def _extra(src):
-    # GX_EXTRA_FLAGS_<source stem>="...": experiments (replaces the per-source defaults when it starts with "=")
-    env = os.environ.get("GX_EXTRA_FLAGS_" + os.path.splitext(src)[0], "")
-    if env.startswith("="):
-        return env[1:].split()
-    return PER_SOURCE_FLAGS.get(src, []) + env.split()
-
-
-BUILD_ID_FILE = os.path.join(LIB_DIR, "BUILD_ID")
 LOCK_FILE = os.path.join(LIB_DIR, ".build.lock")
-
-# The side libraries: the batched cost critic, the state-wise (SCPO), the safety-layer, the USL, the LPG and the
-# one-episode policy step; and the math probe, which only the tests call (the fp32 primitives of gx_device.h and
-# gx_policy.h one by one, tests/test_gpu_math64.py).
-# Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
-# libguardx_hip.so -- and the profiles taken on that build -- alone.
-_SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
-# what the five step libraries share (sizes, the transpose kernel, the MFMA chain, the sample / log-prob block, the host
-# side's checks, dispatch and launches): not the critic library's, whose build id does not cover it
-_STEP_HEADERS = _SIDE_HEADERS + ["gx_step.h"]
-# c_net's device code and the front end of its step and probe kernels, shared by the two learners that correct the action
-# with a Q critic (and by them alone: the other libraries' build ids do not cover them)
-_Q_HEADERS = _STEP_HEADERS + ["gx_qcritic.h", "gx_qstep.h"]
-
-
-class SideLibrary:
-    """One translation unit, one library: libguardx_<key>.so from <sources> with -D<macro>="<source_hash()>" compiled
-    in (its gx?_build_id()), checked at load time by guardx_amd/_sidelib.py."""
-
-    def __init__(self, key, macro, sources, headers):
-        self.key, self.macro, self.sources = key, macro, sources
-        self.headers = headers + [os.path.join("..", "..", "include", "guardx_%s.h" % key)]
-        self.lib = os.path.join(LIB_DIR, "libguardx_%s.so" % key)
-        self.build_id_file = os.path.join(LIB_DIR, key.upper() + "_BUILD_ID")
-
-    def source_hash(self):
-        """source_hash() of this library: its sources, every project header they include, FLAGS and the compiler"""
-        import hashlib
-        h = hashlib.sha256()
-        h.update(compiler_id().encode() + b"\0")
-        for n in sorted(set(self.sources) | set(self.headers)):
-            h.update(n.encode() + b"\0")
-            with open(os.path.join(CSRC, n), "rb") as f:
-                h.update(f.read())
-        h.update(repr(FLAGS).encode())
-        return h.hexdigest()[:24]
-
-    def built_id(self):
-        try:
-            with open(self.build_id_file) as f:
-                return f.read().strip()
-        except OSError:
-            return None
-
-    def needs_build(self):
-        return not os.path.exists(self.lib) or self.built_id() != self.source_hash()
-
-
-LIBRARIES = {lib.key: lib for lib in (
-    SideLibrary("critic", "GXC_BUILD_ID", ["gx_critic.hip"], _SIDE_HEADERS),
-    SideLibrary("statewise", "GXS_BUILD_ID", ["gx_statewise.hip"], _STEP_HEADERS),
-    SideLibrary("safelayer", "GXL_BUILD_ID", ["gx_safelayer.hip"], _STEP_HEADERS),
-    SideLibrary("usl", "GXU_BUILD_ID", ["gx_usl.hip"], _Q_HEADERS),
-    SideLibrary("lpg", "GXP_BUILD_ID", ["gx_lpg.hip"], _Q_HEADERS),
-    SideLibrary("episode", "GXE_BUILD_ID", ["gx_episode.hip"], _STEP_HEADERS),
-    SideLibrary("mathprobe", "GXM_BUILD_ID", ["gx_mathprobe.hip"], _SIDE_HEADERS),
-)}
-# The libraries that work on what the rollouts return: a registry of its own, built after LIBRARIES under the same lock
-# with the same flags, so that the identities of everything above stand.  epstats (the learners' EpRet / EpCost / EpLen
-# bookkeeping, guardx_amd/epstats.py) includes none of the project's device headers.
-POST_LIBRARIES = {lib.key: lib for lib in (
-    SideLibrary("epstats", "GXT_BUILD_ID", ["gx_epstats.hip"], []),
-)}
-
 
 _COMPILER = None
 
@@ -140,8 +62,7 @@ def compiler_id():
     global _COMPILER
     if _COMPILER is None:
         try:
-            out = subprocess.run([os.environ.get("HIPCC", "hipcc"), "--version"], capture_output=True, text=True,
-                                 timeout=60).stdout
+            out = subprocess.run([_hipcc(), "--version"], capture_output=True, text=True, timeout=60).stdout
             keep = [ln.strip() for ln in out.splitlines() if ln.startswith(("HIP version", "AMD clang version"))]
             _COMPILER = "; ".join(keep) or "unknown"
         except Exception:  # noqa: BLE001 - no compiler on this machine: the prebuilt library's own record stands
@@ -149,125 +70,170 @@ def compiler_id():
     return _COMPILER
 
 
-def source_hash():
-    """sha256 over every source, header, flag and the compiler version that goes into the library: the identity of
-    a build.  It is compiled into the library (gx_build_id()) and checked at load time, so a stale or foreign .so
-    is never loaded silently, whatever the file times say (the tree is copied to the GPU box without them)."""
-    import hashlib
-    h = hashlib.sha256()
-    h.update(compiler_id().encode() + b"\0")
-    names = sorted(set(SOURCES) | set(HEADERS) | {"gx_split_rollout.inl"})
-    for n in names:
-        path = os.path.join(CSRC, n)
-        h.update(n.encode() + b"\0")
-        with open(path, "rb") as f:
-            h.update(f.read())
-    h.update(repr((FLAGS, sorted(PER_SOURCE_FLAGS.items()))).encode())
-    return h.hexdigest()[:24]
+class Library:
+    """libguardx_<key>.so from <sources> with -D<macro>="<source_hash()>" compiled in (its gx?_build_id()), checked at
+    load time by guardx_amd/_sidelib.py.  Without `obj_dir` one command compiles and links the sources; with it every
+    source becomes an object there (reused across builds while its `.id` tag stands, compiled in parallel, each with
+    its `per_source_flags`), the first source carries the id and the compiler's name, and the objects are linked."""
 
+    def __init__(self, key, macro, sources, headers, build_id_file, obj_dir=None, per_source_flags=None):
+        self.key, self.macro, self.sources, self.headers = key, macro, sources, headers
+        self.lib = os.path.join(LIB_DIR, "libguardx_%s.so" % key)
+        self.build_id_file = os.path.join(LIB_DIR, build_id_file)
+        self.obj_dir, self.per_source_flags = obj_dir, per_source_flags
 
-def _obj(src):
-    return os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
+    def source_hash(self):
+        """sha256 over every source, every project header they include, the flags and the compiler version that go
+        into the library: the identity of a build.  It is compiled into the library and checked at load time, so a
+        stale or foreign .so is never loaded silently, whatever the file times say (the tree is copied to the GPU box
+        without them)."""
+        import hashlib
+        h = hashlib.sha256()
+        h.update(compiler_id().encode() + b"\0")
+        for n in sorted(set(self.sources) | set(self.headers)):
+            h.update(n.encode() + b"\0")
+            with open(os.path.join(CSRC, n), "rb") as f:
+                h.update(f.read())
+        flags = FLAGS if self.per_source_flags is None else (FLAGS, sorted(self.per_source_flags.items()))
+        h.update(repr(flags).encode())
+        return h.hexdigest()[:24]
 
-
-def built_id():
-    try:
-        with open(BUILD_ID_FILE) as f:
-            return f.read().strip()
-    except OSError:
-        return None
-
-
-def needs_build():
-    return not os.path.exists(LIB) or built_id() != source_hash()
-
-
-def _dep_hash(src):
-    """identity of one object file: its source, every header, its flags (objects are reused across builds)"""
-    import hashlib
-    h = hashlib.sha256()
-    for n in [src] + sorted(set(HEADERS) | {"gx_split_rollout.inl"}):
-        with open(os.path.join(CSRC, n), "rb") as f:
-            h.update(n.encode() + b"\0" + f.read())
-    h.update(repr((FLAGS, _extra(src), compiler_id())).encode())
-    return h.hexdigest()[:24]
-
-
-def build(force=False, verbose=False, jobs=None):
-    """Build under an inter-process lock (several ranks importing at once build once), link to a temporary name
-    and rename into place (nobody can dlopen a half-written file).  All nine libraries; returns the path of
-    libguardx_hip.so."""
-    import fcntl
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    with open(LOCK_FILE, "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
+    def built_id(self):
         try:
-            if force or needs_build():
-                _build_locked(force, verbose, jobs)
-            for side in list(LIBRARIES.values()) + list(POST_LIBRARIES.values()):
-                if force or side.needs_build():
-                    _build_side_locked(side, verbose)
-            return LIB
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
+            with open(self.build_id_file) as f:
+                return f.read().strip()
+        except OSError:
+            return None
 
+    def needs_build(self):
+        return not os.path.exists(self.lib) or self.built_id() != self.source_hash()
 
-def _build_locked(force, verbose, jobs):
-    from concurrent.futures import ThreadPoolExecutor
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    bid = source_hash()
+    def _extra(self, src):
+        # GX_EXTRA_FLAGS_<source stem>="...": experiments (replaces the per-source defaults when it starts with "=")
+        env = os.environ.get("GX_EXTRA_FLAGS_" + os.path.splitext(src)[0], "")
+        if env.startswith("="):
+            return env[1:].split()
+        return self.per_source_flags.get(src, []) + env.split()
 
-    def compile_one(src):
-        path, obj, tag = os.path.join(CSRC, src), _obj(src), _obj(src) + ".id"
-        want = _dep_hash(src) + (":" + bid if src == "gx_api.hip" else "")   # gx_api.hip carries the build id
+    def _obj(self, src):
+        return os.path.join(self.obj_dir, os.path.splitext(src)[0] + ".o")
+
+    def _dep_hash(self, src):
+        """identity of one object file: its source, every header, its flags (objects are reused across builds)"""
+        import hashlib
+        h = hashlib.sha256()
+        for n in [src] + sorted(set(self.headers)):
+            with open(os.path.join(CSRC, n), "rb") as f:
+                h.update(n.encode() + b"\0" + f.read())
+        h.update(repr((FLAGS, self._extra(src), compiler_id())).encode())
+        return h.hexdigest()[:24]
+
+    def _compile(self, src, bid, force, verbose):
+        obj, tag = self._obj(src), self._obj(src) + ".id"
+        carries_id = src == self.sources[0]
+        want = self._dep_hash(src) + (":" + bid if carries_id else "")
         try:
             have = open(tag).read().strip()
         except OSError:
             have = None
         if not force and os.path.exists(obj) and have == want:
             return
-        cmd = [hipcc] + FLAGS + _extra(src) + \
-              (['-DGX_BUILD_ID="%s"' % bid, '-DGX_BUILD_COMPILER="%s"' % compiler_id().replace('"', "'")]
-               if src == "gx_api.hip" else []) + ["-c", path, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+        ids = ['-D%s="%s"' % (self.macro, bid), '-DGX_BUILD_COMPILER="%s"' % compiler_id().replace('"', "'")]
+        _run([_hipcc()] + FLAGS + self._extra(src) + (ids if carries_id else []) +
+             ["-c", os.path.join(CSRC, src), "-o", obj], verbose)
         with open(tag, "w") as f:
             f.write(want)
 
-    jobs = jobs or int(os.environ.get("GX_BUILD_JOBS", "0")) or min(len(SOURCES), os.cpu_count() or 1)
-    with ThreadPoolExecutor(max_workers=jobs) as ex:
-        list(ex.map(compile_one, SOURCES))
-    tmp = LIB + ".tmp.%d" % os.getpid()
-    cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", tmp] + [_obj(s) for s in SOURCES]
+    def build(self, verbose=False, jobs=None, force=False):
+        """Link to a temporary name and rename into place (nobody can dlopen a half-written file), then record the
+        id.  The caller holds the lock (build() below).  `force`: compile the cached objects again too."""
+        bid = self.source_hash()
+        tmp = self.lib + ".tmp.%d" % os.getpid()
+        if self.obj_dir is None:
+            cmd = [_hipcc()] + FLAGS + ['-D%s="%s"' % (self.macro, bid), "-shared", "-o", tmp] + \
+                  [os.path.join(CSRC, s) for s in self.sources]
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            os.makedirs(self.obj_dir, exist_ok=True)
+            jobs = jobs or int(os.environ.get("GX_BUILD_JOBS", "0")) or min(len(self.sources), os.cpu_count() or 1)
+            with ThreadPoolExecutor(max_workers=jobs) as ex:
+                list(ex.map(lambda src: self._compile(src, bid, force, verbose), self.sources))
+            cmd = [_hipcc(), "-shared", "-fPIC", "--offload-arch=gfx950", "-o", tmp] + [self._obj(s) for s in self.sources]
+        _run(cmd, verbose)
+        os.replace(tmp, self.lib)
+        with open(self.build_id_file + ".tmp", "w") as f:
+            f.write(bid + "\n")
+        os.replace(self.build_id_file + ".tmp", self.build_id_file)
+        return self.lib
+
+
+def _hipcc():
+    return os.environ.get("HIPCC", "hipcc")
+
+
+def _run(cmd, verbose):
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    os.replace(tmp, LIB)
-    with open(BUILD_ID_FILE + ".tmp", "w") as f:
-        f.write(bid + "\n")
-    os.replace(BUILD_ID_FILE + ".tmp", BUILD_ID_FILE)
-    return LIB
 
 
-def _build_side_locked(side, verbose):
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    bid = side.source_hash()
-    tmp = side.lib + ".tmp.%d" % os.getpid()
-    cmd = [hipcc] + FLAGS + ['-D%s="%s"' % (side.macro, bid), "-shared", "-o", tmp] + \
-          [os.path.join(CSRC, s) for s in side.sources]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, side.lib)
-    with open(side.build_id_file + ".tmp", "w") as f:
-        f.write(bid + "\n")
-    os.replace(side.build_id_file + ".tmp", side.build_id_file)
-    return side.lib
+# libguardx_hip.so: the engine.  Its hash covers the per-source flags as well; the others' covers FLAGS alone.
+MAIN = Library("hip", "GX_BUILD_ID", SOURCES, HEADERS, "BUILD_ID", obj_dir=os.path.join(LIB_DIR, "obj"),
+               per_source_flags=PER_SOURCE_FLAGS)
+LIB = MAIN.lib
+source_hash, built_id, needs_build = MAIN.source_hash, MAIN.built_id, MAIN.needs_build
+
+# The other libraries, one translation unit each: the batched cost critic, the state-wise (SCPO), the safety-layer, the
+# USL, the LPG and the one-episode policy step; the math probe, which only the tests call (the fp32 primitives of
+# gx_device.h and gx_policy.h one by one, tests/test_gpu_math64.py); and epstats (the learners' EpRet / EpCost / EpLen
+# bookkeeping, guardx_amd/epstats.py), which includes none of the project's device headers.
+# Each is a library of its own with its own build identity, so that it leaves the sources, the flags and the build id of
+# libguardx_hip.so -- and the profiles taken on that build -- alone.
+_SIDE_HEADERS = ["gx_device.h", "gx_policy.h"]
+# what the five step libraries share (sizes, the transpose kernel, the MFMA chain, the sample / log-prob block, the host
+# side's checks, dispatch and launches): not the critic library's, whose build id does not cover it
+_STEP_HEADERS = _SIDE_HEADERS + ["gx_step.h"]
+# c_net's device code and the front end of its step and probe kernels, shared by the two learners that correct the action
+# with a Q critic (and by them alone: the other libraries' build ids do not cover them)
+_Q_HEADERS = _STEP_HEADERS + ["gx_qcritic.h", "gx_qstep.h"]
+
+
+def _side(key, macro, headers):
+    return Library(key, macro, ["gx_%s.hip" % key], headers + [os.path.join("..", "..", "include", "guardx_%s.h" % key)],
+                   key.upper() + "_BUILD_ID")
+
+
+# in build order, after MAIN
+LIBRARIES = {lib.key: lib for lib in (
+    _side("critic", "GXC_BUILD_ID", _SIDE_HEADERS),
+    _side("statewise", "GXS_BUILD_ID", _STEP_HEADERS),
+    _side("safelayer", "GXL_BUILD_ID", _STEP_HEADERS),
+    _side("usl", "GXU_BUILD_ID", _Q_HEADERS),
+    _side("lpg", "GXP_BUILD_ID", _Q_HEADERS),
+    _side("episode", "GXE_BUILD_ID", _STEP_HEADERS),
+    _side("mathprobe", "GXM_BUILD_ID", _SIDE_HEADERS),
+    _side("epstats", "GXT_BUILD_ID", []),
+)}
+
+
+def build(force=False, verbose=False, jobs=None):
+    """Build what needs building under an inter-process lock (several ranks importing at once build once).  All nine
+    libraries; returns the path of libguardx_hip.so."""
+    import fcntl
+    os.makedirs(LIB_DIR, exist_ok=True)
+    with open(LOCK_FILE, "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            for lib in [MAIN] + list(LIBRARIES.values()):
+                if force or lib.needs_build():
+                    lib.build(verbose, jobs, force)
+            return LIB
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in list(LIBRARIES.values()) + list(POST_LIBRARIES.values()):
+    for side in LIBRARIES.values():
         print(side.key, "build id", side.built_id())

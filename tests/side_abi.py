@@ -1,7 +1,5 @@
 """The C header of a side library (include/guardx_<key>.h, prefix gx?_) parsed into ctypes prototypes, and the
-comparison of the library's binding (guardx_amd/_<key>_native.py) with it: shared by the host suites of the statewise,
-the safelayer, the usl and the lpg library; prototypes() also by those of the episode and the mathprobe library (the
-latter has no step_args: tests/test_native_abi.py)."""
+comparison of the library's binding (guardx_amd/_<key>_native.py) with it (tests/test_build_identity.py)."""
 import ctypes as C
 import os
 import re
@@ -38,27 +36,35 @@ def prototypes(key, prefix, step_args):
     return protos
 
 
-def assert_binding_matches_the_header(key, prefix, n, step_args, count):
-    """the `count` prototypes, the fields of gx?_step_args in order and the status values of binding module `n`"""
-    protos = prototypes(key, prefix, step_args)
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == count
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
+def struct_fields(key, prefix):
+    """the fields of gx?_step_args in the header, in order, as ctypes"""
     body = re.search(r"typedef struct %s_step_args \{(.*?)\} %s_step_args;" % (prefix, prefix), header(key), flags=re.S).group(1)
+    base = {"const float*": C.c_void_p, "float*": C.c_void_p, "int32_t*": C.c_void_p, "uint32_t": C.c_uint32,
+            "int32_t": C.c_int32, "float": C.c_float}
     fields = []
     for stmt in body.split(";"):
         stmt = stmt.strip()
         if not stmt:
             continue
-        m = re.match(r"(const float\*|float\*|uint32_t|int32_t|float)\s+(.*)", stmt)
-        base = {"const float*": C.c_void_p, "float*": C.c_void_p, "uint32_t": C.c_uint32, "int32_t": C.c_int32,
-                "float": C.c_float}[m.group(1)]
+        m = re.match(r"(const float\*|float\*|int32_t\*|uint32_t|int32_t|float)\s+(.*)", stmt)
         for nm in m.group(2).split(","):
             nm = nm.strip()
             arr = re.match(r"(\w+)\[(\d+)\]", nm)
-            fields.append((arr.group(1), base * int(arr.group(2))) if arr else (nm, base))
-    assert [(f[0], f[1]) for f in step_args._fields_] == fields
+            fields.append((arr.group(1), base[m.group(1)] * int(arr.group(2))) if arr else (nm, base[m.group(1)]))
+    return fields
+
+
+def assert_binding_matches_the_header(key, prefix, n, step_args, count, values=4):
+    """the `count` prototypes, the fields of gx?_step_args in order (if the library has one) and the `values`
+    enumerators, the four status values among them, of binding module `n`"""
+    protos = prototypes(key, prefix, step_args)
+    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == count
+    for name, (res, args) in protos.items():
+        assert n.SYMBOLS[name] == (res, args), name
+    if step_args is not None:
+        assert [(f[0], f[1]) for f in step_args._fields_] == struct_fields(key, prefix)
     P = prefix.upper()
-    st = dict(re.findall(r"(%s_[A-Z_]+) = (\d+)" % P, header(key)))
-    assert {k: int(v) for k, v in st.items()} == {P + "_" + k: getattr(n, P + "_" + k)
-                                                  for k in ("OK", "ERR_ARG", "ERR_UNSUPPORTED", "ERR_HIP")}
+    have = {k: int(v) for k, v in re.findall(r"\b(%s_[A-Z_0-9]+) = (\d+)" % P, header(key))}
+    assert len(have) == values and have == {k: getattr(n, k) for k in have}
+    assert {k: have[P + "_" + k] for k in ("OK", "ERR_ARG", "ERR_UNSUPPORTED", "ERR_HIP")} == \
+        {"OK": 0, "ERR_ARG": 1, "ERR_UNSUPPORTED": 2, "ERR_HIP": 4}

@@ -1,5 +1,5 @@
-"""The host side of Engine.rollout_episode (the `*_one_episode` learners on the device path): the seventh library's build
-identity and ABI, its argument checks, its device code, and the batch helper's host-tensor path against a numpy
+"""The host side of Engine.rollout_episode (the `*_one_episode` learners on the device path): the seventh library's
+argument checks and device code (its build identity and ABI: tests/test_build_identity.py), and the batch helper's host-tensor path against a numpy
 restatement of the one-episode buffer (safe_rl_libX/trpo_one_episode/trpo.py:24-132, cpo_one_episode/cpo.py:22-156)."""
 import ctypes as C
 import os
@@ -9,101 +9,16 @@ import numpy as np
 import pytest
 
 from oracle.trpo_buffer_np import discount_cumsum
-import side_abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_SYMBOLS = 10
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# build identity and ABI
+# device code and argument checks (build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_episode_source_hash_covers_its_sources():
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    assert list(libs) == ["critic", "statewise", "safelayer", "usl", "lpg", "episode", "mathprobe"]
-    ep = libs["episode"]
-    assert ep.sources == ["gx_episode.hip"] and ep.macro == "GXE_BUILD_ID"
-    incs = [i for f in ("gx_episode.hip", "gx_step.h")
-            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in ep.headers}
-    assert {norm(i) for i in incs} <= have
-    assert "gx_step.h" in incs and norm("gx_device.h") in have        # gx_policy.h's own include
-    # its own library: nothing of it is hashed into the six older ones, whose identities stand
-    older = set(build.SOURCES) | {s for k, l in libs.items() if k != "episode" for s in l.sources}
-    assert not (set(ep.sources) & older)
-    assert all("episode" not in h for h in build.HEADERS + [h for k, l in libs.items() if k != "episode" for h in l.headers])
-    recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
-    assert build.source_hash() == recorded
-    ids = {l.source_hash() for l in libs.values()} | {build.source_hash()}
-    assert len(ids) == 8 and len(ep.source_hash()) == 24      # (the eighth: the tests' math probe, younger than this one)
-    # the critic library's file list is what it was: the step core is not part of it
-    assert libs["critic"].sources == ["gx_critic.hip"]
-    assert libs["critic"].headers == ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_critic.h")]
-    assert os.path.basename(ep.build_id_file) == "EPISODE_BUILD_ID"
-    assert "guardx_amd/lib/EPISODE_BUILD_ID" in open(os.path.join(ROOT, ".gitignore")).read().split()
-
-
-def _struct_fields(key, prefix):
-    """the fields of gx?_step_args in the header, in order, as ctypes (side_abi's reading, with int32_t* state arrays)"""
-    body = re.search(r"typedef struct %s_step_args \{(.*?)\} %s_step_args;" % (prefix, prefix), side_abi.header(key), flags=re.S).group(1)
-    base = {"const float*": C.c_void_p, "float*": C.c_void_p, "int32_t*": C.c_void_p, "uint32_t": C.c_uint32,
-            "int32_t": C.c_int32, "float": C.c_float}
-    fields = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        m = re.match(r"(const float\*|float\*|int32_t\*|uint32_t|int32_t|float)\s+(.*)", stmt)
-        for nm in m.group(2).split(","):
-            nm = nm.strip()
-            arr = re.match(r"(\w+)\[(\d+)\]", nm)
-            fields.append((arr.group(1), base[m.group(1)] * int(arr.group(2))) if arr else (nm, base[m.group(1)]))
-    return fields
-
-
-def test_binding_matches_the_header():
-    from guardx_amd import _episode_native as n
-    protos = side_abi.prototypes("episode", "gxe", n.GxeStepArgs)
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == N_SYMBOLS
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    assert [(f[0], f[1]) for f in n.GxeStepArgs._fields_] == _struct_fields("episode", "gxe")
-    st = dict(re.findall(r"(GXE_[A-Z_]+) = (\d+)", side_abi.header("episode")))
-    assert {k: int(v) for k, v in st.items()} == {"GXE_" + k: getattr(n, "GXE_" + k)
-                                                  for k in ("OK", "ERR_ARG", "ERR_UNSUPPORTED", "ERR_HIP")}
-
-
 @pytest.fixture(scope="module")
 def ep_lib():
     from guardx_amd import build, _episode_native
     build.build()                      # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     return _episode_native.load()      # refuses a library whose build id is not the tree's
-
-
-def test_export_list_and_build_id_round_trip(ep_lib):
-    import subprocess
-    from guardx_amd import build, _episode_native as n, _native, _critic_native, _statewise_native, _safelayer_native, \
-        _usl_native, _lpg_native
-    libs = build.LIBRARIES
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxe_", ln))
-    assert exported == sorted(side_abi.prototypes("episode", "gxe", n.GxeStepArgs))
-    assert ep_lib.gxe_build_id().decode() == libs["episode"].source_hash() == libs["episode"].built_id()
-    for other in (_native, _critic_native, _statewise_native, _safelayer_native, _usl_native, _lpg_native):
-        lib = C.CDLL(other.LIB_PATH)
-        assert not any(hasattr(lib, s) for s in n.SYMBOLS)
-
-
-def test_a_foreign_build_id_is_refused(ep_lib, monkeypatch):
-    from guardx_amd import build, _episode_native as n
-    libs = build.LIBRARIES
-    monkeypatch.setattr(n._side, "_lib", None)
-    monkeypatch.setattr(libs["episode"], "source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(libs["episode"], "needs_build", lambda: False)
-    with pytest.raises(ImportError, match="built from other sources"):
-        n.load()
 
 
 def test_no_scratch_in_the_device_code(tmp_path):

@@ -1,8 +1,7 @@
 """The host side of guardx_amd.epstats (the learners' EpRet / EpCost / EpLen / EpCostRet / MaxEpLenRet / VVals from a
 rollout's (T, N) tensors): its host-tensor path against the independent restatement of the learner loop
-(tests/epstats64.py), the fixed order of its float64 sums, and the ninth library's build identity, ABI, argument checks
-and device code."""
-import ctypes as C
+(tests/epstats64.py), the fixed order of its float64 sums, and the ninth library's argument checks and device code
+(its build identity and ABI: tests/test_build_identity.py)."""
 import math
 import os
 import re
@@ -13,10 +12,7 @@ import pytest
 import torch
 
 import epstats64 as e64
-import side_abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_SYMBOLS = 5
 STAT_KEYS = ('EpRet', 'EpCost', 'EpLen', 'EpCostRet', 'MaxEpLenRet', 'VVals')
 
 
@@ -301,76 +297,13 @@ def test_planted_mistakes_are_told_apart(mistake):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# build identity and ABI of libguardx_epstats.so
+# libguardx_epstats.so: its argument checks and its device code (build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-# source_hash() of the eight libraries that were there before this one, under the compiler profiles/r05_build_id.txt records
-IDS_BEFORE_EPSTATS = {"hip": "3d06e0f4bcfa769a89bb163e", "critic": "1afdcabad09cc0d419a8d9a5",
-                      "statewise": "e6d760b1dbf2d5195c1247e0", "safelayer": "de39af70500c88f6609d39c8",
-                      "usl": "34485803dc952d5454f49150", "lpg": "e196100c68b94afce543fb6f",
-                      "episode": "2ac1225ff7d697761c70297a", "mathprobe": "1500249652e842aae76b306b"}
-
-
-def test_epstats_is_a_library_of_its_own_and_leaves_the_older_ones_alone():
-    from guardx_amd import build
-    assert list(build.LIBRARIES) == ["critic", "statewise", "safelayer", "usl", "lpg", "episode", "mathprobe"]
-    assert list(build.POST_LIBRARIES) == ["epstats"]
-    ep = build.POST_LIBRARIES["epstats"]
-    assert ep.sources == ["gx_epstats.hip"] and ep.macro == "GXT_BUILD_ID"
-    assert ep.headers == [os.path.join("..", "..", "include", "guardx_epstats.h")]
-    incs = re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, "gx_epstats.hip")).read())
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    assert [norm(i) for i in incs] == [norm(h) for h in ep.headers]   # its hash covers exactly what it is built from
-    older = set(build.SOURCES) | {s for lib in build.LIBRARIES.values() for s in lib.sources}
-    assert not (set(ep.sources) & older)
-    assert all("epstats" not in h for h in build.HEADERS + [h for lib in build.LIBRARIES.values() for h in lib.headers])
-    ids = dict({k: lib.source_hash() for k, lib in build.LIBRARIES.items()}, hip=build.source_hash())
-    assert len(set(ids.values()) | {ep.source_hash()}) == 9 and len(ep.source_hash()) == 24
-    recorded, compiler = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split(None, 1)
-    assert ids["hip"] == recorded == IDS_BEFORE_EPSTATS["hip"]
-    if build.compiler_id() in compiler:
-        assert ids == IDS_BEFORE_EPSTATS
-    assert os.path.basename(ep.build_id_file) == "EPSTATS_BUILD_ID"
-    assert "guardx_amd/lib/EPSTATS_BUILD_ID" in open(os.path.join(ROOT, ".gitignore")).read().split()
-
-
-def test_binding_matches_the_header():
-    from guardx_amd import _epstats_native as n
-    protos = side_abi.prototypes("epstats", "gxt", None)
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == N_SYMBOLS
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    values = {k: int(v) for k, v in re.findall(r"\b(GXT_[A-Z_]+) = (\d+)", side_abi.header("epstats"))}
-    assert len(values) == 4 + 8 and values == {k: getattr(n, k) for k in values}
-    assert {k: values["GXT_" + k] for k in ("OK", "ERR_ARG", "ERR_UNSUPPORTED", "ERR_HIP")} == \
-        {"OK": 0, "ERR_ARG": 1, "ERR_UNSUPPORTED": 2, "ERR_HIP": 4}
-
-
 @pytest.fixture(scope="module")
 def lib():
     from guardx_amd import build, _epstats_native
     build.build()                      # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     return _epstats_native.load()      # refuses a library whose build id is not the tree's
-
-
-def test_export_list_and_build_id_round_trip(lib):
-    from guardx_amd import build, _epstats_native as n, _native, _critic_native, _episode_native, _mathprobe_native
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxt_", ln))
-    assert exported == sorted(side_abi.prototypes("epstats", "gxt", None))
-    side = build.POST_LIBRARIES["epstats"]
-    assert lib.gxt_build_id().decode() == side.source_hash() == side.built_id()
-    for other in (_native, _critic_native, _episode_native, _mathprobe_native):
-        assert not any(hasattr(C.CDLL(other.LIB_PATH), s) for s in n.SYMBOLS)
-
-
-def test_a_foreign_build_id_is_refused(lib, monkeypatch):
-    from guardx_amd import build, _epstats_native as n
-    side = build.POST_LIBRARIES["epstats"]
-    monkeypatch.setattr(n._side, "_lib", None)
-    monkeypatch.setattr(side, "source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(side, "needs_build", lambda: False)
-    with pytest.raises(ImportError, match="built from other sources"):
-        n.load()
 
 
 def test_sizes_and_bad_arguments_are_errors_not_crashes(lib):

@@ -1,9 +1,8 @@
-"""The host side of Engine.rollout_lpg (LPG's gradient projection on the device path): the sixth library's build identity
-and ABI, the shared c_net header's place in the build ids, the float64 gradient at the zero action against torch autograd,
+"""The host side of Engine.rollout_lpg (LPG's gradient projection on the device path): the sixth library's device code
+and argument checks (its build identity and ABI: tests/test_build_identity.py), the float64 gradient at the zero action against torch autograd,
 the float32 projection against the float64 one, the batch helper against a numpy restatement of the buffer, and the
 sizing of the GPU tests' probe inputs."""
 import ctypes as C
-import hashlib
 import os
 import re
 
@@ -11,10 +10,8 @@ import numpy as np
 import pytest
 
 import lpg64
-import side_abi
 import usl64
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the bound on a_safe is informative: on at least 90 % of the corrected rows of every probe case it is below
 # C_INFORMATIVE (1 + |a_safe|).  Chosen here, on the CPU, from the float64 restatement alone.
@@ -22,91 +19,13 @@ C_INFORMATIVE = 1e-3
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# build identity and ABI
+# device code and argument checks (build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_lpg_source_hash_covers_its_sources_and_the_shared_header():
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    assert libs["lpg"].sources == ["gx_lpg.hip"] and libs["lpg"].macro == "GXP_BUILD_ID"
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in libs["lpg"].headers}
-    incs = set()
-    for f in ("gx_lpg.hip", "gx_qstep.h", "gx_qcritic.h", "gx_step.h"):
-        incs |= {norm(i) for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())}
-    assert incs <= have and norm("gx_qstep.h") in incs
-    assert {norm("gx_qstep.h"), norm("gx_qcritic.h"), norm("gx_device.h"), norm("../../include/guardx_lpg.h")} <= have
-    assert {norm("gx_qcritic.h"), norm("gx_qstep.h")} <= {norm(h) for h in libs["usl"].headers}
-    assert not any("qstep" in h for key, lib in libs.items() if key not in ("usl", "lpg") for h in lib.headers)
-    assert not any("qstep" in h for h in build.HEADERS + build.SOURCES)
-    assert len(libs["lpg"].source_hash()) == 24
-
-
-def test_the_older_build_ids_do_not_cover_the_shared_header():
-    """critic hashes exactly the file list it hashed before gx_qcritic.h existed (its source, gx_device.h, gx_policy.h and
-    its own header), statewise and safelayer that list and gx_step.h, and libguardx_hip.so's id is still the recorded one"""
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    for key, src, step in (("critic", "gx_critic.hip", []), ("statewise", "gx_statewise.hip", ["gx_step.h"]),
-                           ("safelayer", "gx_safelayer.hip", ["gx_step.h"])):
-        lib = libs[key]
-        names = [src, "gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_%s.h" % key)] + step
-        assert sorted(set(lib.sources) | set(lib.headers)) == sorted(names)
-        assert not any("qcritic" in h or "lpg" in h for h in lib.headers)
-        h = hashlib.sha256()
-        h.update(build.compiler_id().encode() + b"\0")
-        for n in sorted(names):
-            h.update(n.encode() + b"\0")
-            with open(os.path.join(build.CSRC, n), "rb") as f:
-                h.update(f.read())
-        h.update(repr(build.FLAGS).encode())
-        assert lib.source_hash() == h.hexdigest()[:24], key
-    assert not any("qcritic" in h or "lpg" in h for h in build.HEADERS + build.SOURCES)
-    assert "gx_step.h" not in build.HEADERS + build.SOURCES
-    recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
-    assert build.source_hash() == recorded
-    ids = {lib.source_hash() for lib in libs.values()} | {build.source_hash()}
-    assert len(ids) == len(libs) + 1                            # all distinct
-
-
-def _prototypes():
-    from guardx_amd._lpg_native import GxpStepArgs
-    return side_abi.prototypes("lpg", "gxp", GxpStepArgs)
-
-
-def test_binding_matches_the_header():
-    from guardx_amd import _lpg_native as n
-    side_abi.assert_binding_matches_the_header("lpg", "gxp", n, n.GxpStepArgs, 9)
-
-
 @pytest.fixture(scope="module")
 def lpg_lib():
     from guardx_amd import build, _lpg_native
     build.build()                      # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     return _lpg_native.load()          # refuses a library whose build id is not the tree's
-
-
-def test_export_list_and_build_id_round_trip(lpg_lib):
-    import subprocess
-    from guardx_amd import build, _lpg_native as n, _native, _critic_native, _statewise_native, _safelayer_native, _usl_native
-    libs = build.LIBRARIES
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gx", ln))
-    assert exported == sorted(_prototypes())
-    assert lpg_lib.gxp_build_id().decode() == libs["lpg"].source_hash() == libs["lpg"].built_id()
-    for other in (_native.LIB_PATH, _critic_native.LIB_PATH, _statewise_native.LIB_PATH, _safelayer_native.LIB_PATH,
-                  _usl_native.LIB_PATH):
-        lib = C.CDLL(other)
-        assert not any(hasattr(lib, s) for s in n.SYMBOLS)
-
-
-def test_a_foreign_build_id_is_refused(lpg_lib, monkeypatch):
-    from guardx_amd import build, _lpg_native as n
-    libs = build.LIBRARIES
-    monkeypatch.setattr(n._side, "_lib", None)
-    monkeypatch.setattr(libs["lpg"], "source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(libs["lpg"], "needs_build", lambda: False)
-    with pytest.raises(ImportError, match="built from other sources"):
-        n.load()
 
 
 def test_no_scratch_in_the_device_code(tmp_path):

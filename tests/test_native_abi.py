@@ -163,87 +163,13 @@ def test_lane_group_steps_contain_no_call():
 
 # ---------------------------------------------------------------------------------------------------------------------
 # libguardx_mathprobe.so (include/guardx_mathprobe.h): the tests' own library, held to what the side libraries are held to
+# (its build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-# what the seven libraries of the product were built from when the probe was added: it touches none of their sources,
-# headers or flags, so these stand (the compiler is part of them; they are compared only under the recorded compiler)
-IDS_BEFORE_THE_PROBE = {"hip": "3d06e0f4bcfa769a89bb163e", "critic": "1afdcabad09cc0d419a8d9a5",
-                        "statewise": "e6d760b1dbf2d5195c1247e0", "safelayer": "de39af70500c88f6609d39c8",
-                        "usl": "34485803dc952d5454f49150", "lpg": "e196100c68b94afce543fb6f",
-                        "episode": "2ac1225ff7d697761c70297a"}
-
-
-def test_mathprobe_source_hash_covers_its_sources_and_leaves_the_other_libraries_alone():
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    mp = libs["mathprobe"]
-    assert list(libs)[-1] == "mathprobe" and len(libs) == 7
-    assert mp.sources == ["gx_mathprobe.hip"] and mp.macro == "GXM_BUILD_ID"
-    assert mp.headers == ["gx_device.h", "gx_policy.h", os.path.join("..", "..", "include", "guardx_mathprobe.h")]
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    incs = [i for f in ("gx_mathprobe.hip", "gx_policy.h")
-            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
-    assert {norm(i) for i in incs} <= {norm(h) for h in mp.headers} and "gx_policy.h" in incs and "gx_device.h" in incs
-    others = set(build.SOURCES) | {s for k, l in libs.items() if k != "mathprobe" for s in l.sources}
-    assert not (set(mp.sources) & others)
-    assert all("mathprobe" not in h for h in build.HEADERS + [h for k, l in libs.items() if k != "mathprobe" for h in l.headers])
-    ids = dict({k: l.source_hash() for k, l in libs.items()}, hip=build.source_hash())
-    assert len(set(ids.values())) == 8 and len(mp.source_hash()) == 24
-    recorded, compiler = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split(None, 1)
-    assert ids["hip"] == recorded == IDS_BEFORE_THE_PROBE["hip"]
-    if build.compiler_id() in compiler:
-        assert {k: v for k, v in ids.items() if k != "mathprobe"} == IDS_BEFORE_THE_PROBE
-    assert os.path.basename(mp.build_id_file) == "MATHPROBE_BUILD_ID"
-    assert "guardx_amd/lib/MATHPROBE_BUILD_ID" in open(os.path.join(ROOT, ".gitignore")).read().split()
-
-
-def test_mathprobe_binding_matches_the_header():
-    import side_abi
-    from guardx_amd import _mathprobe_native as n
-    protos = side_abi.prototypes("mathprobe", "gxm", None)
-    assert sorted(protos) == sorted(n.SYMBOLS) and len(protos) == 5
-    for name, (res, args) in protos.items():
-        assert n.SYMBOLS[name] == (res, args), name
-    hdr = side_abi.header("mathprobe")
-    values = {k: int(v) for k, v in re.findall(r"\b(GXM_[A-Z_0-9]+) = (\d+)", hdr)}
-    assert len(values) == 4 + 12 + 5 and values == {k: getattr(n, k) for k in values}
-    assert int(re.search(r"#define GXM_REPORT_LOWEST (\d+)", hdr).group(1)) == n.GXM_REPORT_LOWEST == 16
-    body = re.search(r"typedef struct gxm_sweep_report \{(.*?)\} gxm_sweep_report;", hdr, flags=re.S).group(1)
-    fields = re.findall(r"(uint64_t|uint32_t)\s+(\w+)(?:\[(\w+)\])?;", body)
-    base = {"uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
-    want = [(nm, base[t] * int(values.get(k, n.GXM_REPORT_LOWEST if k == "GXM_REPORT_LOWEST" else k)) if k else base[t])
-            for t, nm, k in fields]
-    assert [(f[0], f[1]) for f in n.GxmSweepReport._fields_] == want and C.sizeof(n.GxmSweepReport) == 80
-
-
 @pytest.fixture(scope="module")
 def mathprobe_lib():
     from guardx_amd import build, _mathprobe_native
     build.build()                       # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     return _mathprobe_native.load()     # refuses a library whose build id is not the tree's
-
-
-def test_mathprobe_export_list_and_build_id_round_trip(mathprobe_lib, native):
-    import subprocess
-    from guardx_amd import build, _mathprobe_native as n, _critic_native, _statewise_native, _safelayer_native, _usl_native, \
-        _lpg_native, _episode_native
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gx", ln))
-    assert exported == sorted(n.SYMBOLS)
-    mp = build.LIBRARIES["mathprobe"]
-    assert mathprobe_lib.gxm_build_id().decode() == mp.source_hash() == mp.built_id()
-    for other in (native, _critic_native, _statewise_native, _safelayer_native, _usl_native, _lpg_native, _episode_native):
-        lib = C.CDLL(other.LIB_PATH)
-        assert not any(hasattr(lib, s) for s in n.SYMBOLS)
-
-
-def test_mathprobe_foreign_build_id_is_refused(mathprobe_lib, monkeypatch):
-    from guardx_amd import build, _mathprobe_native as n
-    mp = build.LIBRARIES["mathprobe"]
-    monkeypatch.setattr(n._side, "_lib", None)
-    monkeypatch.setattr(mp, "source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(mp, "needs_build", lambda: False)
-    with pytest.raises(ImportError, match="built from other sources"):
-        n.load()
 
 
 def test_mathprobe_bad_arguments_are_errors_not_crashes(mathprobe_lib):

@@ -1,5 +1,5 @@
 """The host side of Engine.rollout_safelayer (the safety layer on the device path): packing g_net, the fourth library's
-build identity and ABI, the float32 transcription of the correction against the float64 one, the batch helper against a
+device code and argument checks (its build identity and ABI: tests/test_build_identity.py), the float32 transcription of the correction against the float64 one, the batch helper against a
 numpy restatement of SafeLayerBufferX, and the sizing of the GPU tests' inputs on the CPU checker's engine."""
 import ctypes as C
 import os
@@ -12,9 +12,7 @@ from oracle import policy64
 from oracle.trpo_buffer_np import TRPOBufferNP
 from helpers import task_config
 import safelayer64
-import side_abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _seq(D, h, A, tail=(), act=None, h2=None):
@@ -89,81 +87,13 @@ def test_correction32_against_correction64():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# build identity and ABI
+# device code and argument checks (build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_safelayer_source_hash_covers_its_sources():
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    assert libs["safelayer"].sources == ["gx_safelayer.hip"]
-    incs = [i for f in ("gx_safelayer.hip", "gx_step.h")
-            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in libs["safelayer"].headers}
-    assert {norm(i) for i in incs} <= have
-    assert "gx_step.h" in incs and norm("gx_device.h") in have        # gx_policy.h's own include
-    # its own library: nothing of it is hashed into the three older ones, whose identities stand
-    older = set(build.SOURCES) | set(libs["critic"].sources) | set(libs["statewise"].sources)
-    assert not (set(libs["safelayer"].sources) & older)
-    assert all("safelayer" not in h for h in build.HEADERS + libs["critic"].headers + libs["statewise"].headers)
-    recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
-    assert build.source_hash() == recorded
-    ids = {libs["safelayer"].source_hash(), libs["statewise"].source_hash(), libs["critic"].source_hash(), build.source_hash()}
-    assert len(ids) == 4 and len(libs["safelayer"].source_hash()) == 24
-
-
-def test_safelayer_hash_changes_with_a_source(monkeypatch, tmp_path):
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    before = libs["safelayer"].source_hash()
-    for n in ["gx_safelayer.hip", "gx_device.h", "gx_policy.h", "gx_step.h"]:
-        (tmp_path / n).write_bytes(open(os.path.join(build.CSRC, n), "rb").read())
-    inc = tmp_path.parent / "include_sl"
-    inc.mkdir(exist_ok=True)
-    hdr = open(os.path.join(ROOT, "include", "guardx_safelayer.h"), "rb").read()
-    (inc / "guardx_safelayer.h").write_bytes(hdr + b"\n")
-    monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    monkeypatch.setattr(libs["safelayer"], "headers", ["gx_device.h", "gx_policy.h", "gx_step.h", os.path.join("..", "include_sl", "guardx_safelayer.h")])
-    assert libs["safelayer"].source_hash() != before                    # the header is part of the identity
-
-
-def _prototypes():
-    from guardx_amd._safelayer_native import GxlStepArgs
-    return side_abi.prototypes("safelayer", "gxl", GxlStepArgs)
-
-
-def test_binding_matches_the_header():
-    from guardx_amd import _safelayer_native as n
-    side_abi.assert_binding_matches_the_header("safelayer", "gxl", n, n.GxlStepArgs, 8)
-
-
 @pytest.fixture(scope="module")
 def sl_lib():
     from guardx_amd import build, _safelayer_native
     build.build()                      # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     return _safelayer_native.load()    # refuses a library whose build id is not the tree's
-
-
-def test_export_list_and_build_id_round_trip(sl_lib):
-    import subprocess
-    from guardx_amd import build, _safelayer_native as n, _native, _critic_native, _statewise_native
-    libs = build.LIBRARIES
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxl_", ln))
-    assert exported == sorted(_prototypes())
-    assert sl_lib.gxl_build_id().decode() == libs["safelayer"].source_hash() == libs["safelayer"].built_id()
-    for other in (_native.LIB_PATH, _critic_native.LIB_PATH, _statewise_native.LIB_PATH):
-        lib = C.CDLL(other)
-        assert not any(hasattr(lib, s) for s in n.SYMBOLS)
-
-
-def test_a_foreign_build_id_is_refused(sl_lib, monkeypatch):
-    from guardx_amd import build, _safelayer_native as n
-    libs = build.LIBRARIES
-    monkeypatch.setattr(n._side, "_lib", None)
-    monkeypatch.setattr(libs["safelayer"], "source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(libs["safelayer"], "needs_build", lambda: False)
-    with pytest.raises(ImportError, match="built from other sources"):
-        n.load()
 
 
 def test_no_scratch_in_the_device_code(tmp_path):

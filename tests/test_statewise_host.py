@@ -1,5 +1,5 @@
 """The host side of Engine.rollout_statewise (SCPO on the device path): packing the Softplus-headed cost critic, the
-third library's build identity and ABI, the M recurrence against SCPO's loop as written and as intended, and the numpy
+third library's device code and argument checks (its build identity and ABI: tests/test_build_identity.py), the M recurrence against SCPO's loop as written and as intended, and the numpy
 restatement of SCPOBufferX the device batch helper is checked against (tests/test_gpu_statewise.py)."""
 import ctypes as C
 import os
@@ -9,9 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.trpo_buffer_np import TRPOBufferNP, discount_cumsum
-import side_abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _seq(D, h, tail=()):
@@ -63,70 +61,13 @@ def test_scpo_actor_critic_packs_on_the_augmented_width():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# build identity and ABI
+# device code and argument checks (build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_statewise_source_hash_covers_its_sources():
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    assert libs["statewise"].sources == ["gx_statewise.hip"]
-    incs = [i for f in ("gx_statewise.hip", "gx_step.h")
-            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in libs["statewise"].headers}
-    assert {norm(i) for i in incs} <= have
-    assert "gx_step.h" in incs and norm("gx_device.h") in have        # gx_policy.h's own include
-    # its own library: nothing of it is hashed into the main library or the critic's, whose identities stand
-    assert not (set(libs["statewise"].sources) & (set(build.SOURCES) | set(libs["critic"].sources)))
-    assert all("statewise" not in h for h in build.HEADERS + libs["critic"].headers)
-    recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
-    assert build.source_hash() == recorded
-    assert len(libs["statewise"].source_hash()) == 24
-    assert len({libs["statewise"].source_hash(), libs["critic"].source_hash(), build.source_hash()}) == 3
-
-
-def test_statewise_hash_changes_with_a_source(monkeypatch, tmp_path):
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    before = libs["statewise"].source_hash()
-    for n in ["gx_statewise.hip", "gx_device.h", "gx_policy.h", "gx_step.h"]:
-        (tmp_path / n).write_bytes(open(os.path.join(build.CSRC, n), "rb").read())
-    inc = tmp_path.parent / "include_sw"
-    inc.mkdir(exist_ok=True)
-    hdr = open(os.path.join(ROOT, "include", "guardx_statewise.h"), "rb").read()
-    (inc / "guardx_statewise.h").write_bytes(hdr + b"\n")
-    monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    monkeypatch.setattr(libs["statewise"], "headers", ["gx_device.h", "gx_policy.h", "gx_step.h", os.path.join("..", "include_sw", "guardx_statewise.h")])
-    assert libs["statewise"].source_hash() != before                    # the header is part of the identity
-
-
-def _prototypes():
-    from guardx_amd._statewise_native import GxsStepArgs
-    return side_abi.prototypes("statewise", "gxs", GxsStepArgs)
-
-
-def test_binding_matches_the_header():
-    from guardx_amd import _statewise_native as n
-    side_abi.assert_binding_matches_the_header("statewise", "gxs", n, n.GxsStepArgs, 7)
-
-
 @pytest.fixture(scope="module")
 def sw_lib():
     from guardx_amd import build, _statewise_native
     build.build()
     return _statewise_native.load()
-
-
-def test_export_list_equals_the_header(sw_lib):
-    import subprocess
-    from guardx_amd import build, _statewise_native as n, _native, _critic_native
-    libs = build.LIBRARIES
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxs_", ln))
-    assert exported == sorted(_prototypes())
-    assert sw_lib.gxs_build_id().decode() == libs["statewise"].source_hash() == libs["statewise"].built_id()
-    for other in (_native.LIB_PATH, _critic_native.LIB_PATH):
-        lib = C.CDLL(other)
-        assert not any(hasattr(lib, s) for s in n.SYMBOLS)
 
 
 def test_no_scratch_in_the_device_code(tmp_path):

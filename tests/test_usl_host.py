@@ -1,5 +1,5 @@
 """The host side of Engine.rollout_usl (USL's gradient-descent safety loop on the device path): packing c_net, the fifth
-library's build identity and ABI, the float64 analytic gradient against torch autograd, the float32 update against the
+library's device code and argument checks (its build identity and ABI: tests/test_build_identity.py), the float64 analytic gradient against torch autograd, the float32 update against the
 float64 one, the batch helper against a numpy restatement of USLBufferX, and the sizing of the GPU tests' probe inputs."""
 import ctypes as C
 import os
@@ -9,10 +9,8 @@ import numpy as np
 import pytest
 
 from oracle.trpo_buffer_np import TRPOBufferNP
-import side_abi
 import usl64
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _seq(D, h, out=1, tail=None, act=None, h2=None):
@@ -53,68 +51,13 @@ def test_pack_q_critic():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# build identity and ABI
+# device code and argument checks (build identity and ABI: tests/test_build_identity.py)
 # ---------------------------------------------------------------------------------------------------------------------
-def test_usl_source_hash_covers_its_sources_and_leaves_the_older_libraries_alone():
-    from guardx_amd import build
-    libs = build.LIBRARIES
-    assert libs["usl"].sources == ["gx_usl.hip"]
-    incs = [i for f in ("gx_usl.hip", "gx_qstep.h", "gx_qcritic.h", "gx_step.h")
-            for i in re.findall(r'#include "([^"]+)"', open(os.path.join(build.CSRC, f)).read())]
-    norm = lambda p: os.path.normpath(os.path.join(build.CSRC, p))   # noqa: E731
-    have = {norm(h) for h in libs["usl"].headers}
-    assert {norm(i) for i in incs} <= have and {norm("gx_device.h"), norm("gx_qcritic.h"), norm("gx_qstep.h")} <= have
-    assert "gx_qstep.h" in incs and norm("gx_qstep.h") in {norm(h) for h in libs["lpg"].headers}
-    assert not any("qstep" in h for key, lib in libs.items() if key not in ("usl", "lpg") for h in lib.headers)
-    assert not any("qstep" in h for h in build.HEADERS + build.SOURCES)
-    older = set(build.SOURCES) | set(libs["critic"].sources) | set(libs["statewise"].sources) | set(libs["safelayer"].sources)
-    assert not (set(libs["usl"].sources) & older)
-    assert all("usl" not in h for h in build.HEADERS + libs["critic"].headers + libs["statewise"].headers + libs["safelayer"].headers)
-    recorded = open(os.path.join(ROOT, "profiles", "r05_build_id.txt")).read().split()[0]
-    assert build.source_hash() == recorded
-    ids = {libs["usl"].source_hash(), libs["safelayer"].source_hash(), libs["statewise"].source_hash(),
-           libs["critic"].source_hash(), build.source_hash()}
-    assert len(ids) == 5 and len(libs["usl"].source_hash()) == 24
-
-
-def _prototypes():
-    from guardx_amd._usl_native import GxuStepArgs
-    return side_abi.prototypes("usl", "gxu", GxuStepArgs)
-
-
-def test_binding_matches_the_header():
-    from guardx_amd import _usl_native as n
-    side_abi.assert_binding_matches_the_header("usl", "gxu", n, n.GxuStepArgs, 9)
-
-
 @pytest.fixture(scope="module")
 def usl_lib():
     from guardx_amd import build, _usl_native
     build.build()                      # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     return _usl_native.load()          # refuses a library whose build id is not the tree's
-
-
-def test_export_list_and_build_id_round_trip(usl_lib):
-    import subprocess
-    from guardx_amd import build, _usl_native as n, _native, _critic_native, _statewise_native, _safelayer_native
-    libs = build.LIBRARIES
-    out = subprocess.run(["nm", "-D", "--defined-only", n.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if re.search(r"\sT\s+gxu_", ln))
-    assert exported == sorted(_prototypes())
-    assert usl_lib.gxu_build_id().decode() == libs["usl"].source_hash() == libs["usl"].built_id()
-    for other in (_native.LIB_PATH, _critic_native.LIB_PATH, _statewise_native.LIB_PATH, _safelayer_native.LIB_PATH):
-        lib = C.CDLL(other)
-        assert not any(hasattr(lib, s) for s in n.SYMBOLS)
-
-
-def test_a_foreign_build_id_is_refused(usl_lib, monkeypatch):
-    from guardx_amd import build, _usl_native as n
-    libs = build.LIBRARIES
-    monkeypatch.setattr(n._side, "_lib", None)
-    monkeypatch.setattr(libs["usl"], "source_hash", lambda: "0" * 24)
-    monkeypatch.setattr(libs["usl"], "needs_build", lambda: False)
-    with pytest.raises(ImportError, match="built from other sources"):
-        n.load()
 
 
 def test_no_scratch_in_the_device_code(tmp_path):

@@ -15,8 +15,7 @@ from guardx_amd import build as b  # noqa: E402
 
 tag = sys.argv[1]
 vdir = os.path.join(b.LIB_DIR, "variants")
-b.OBJ_DIR = os.path.join(vdir, "obj_" + tag)
-b.LIB = os.path.join(vdir, f"libguardx_hip_{tag}.so")
-b.BUILD_ID_FILE = os.path.join(vdir, f"BUILD_ID_{tag}")
-os.makedirs(b.OBJ_DIR, exist_ok=True)
-print(b._build_locked(False, "-v" in sys.argv, None))
+variant = b.Library(b.MAIN.key, b.MAIN.macro, b.SOURCES, b.HEADERS, os.path.join(vdir, f"BUILD_ID_{tag}"),
+                    obj_dir=os.path.join(vdir, "obj_" + tag), per_source_flags=b.PER_SOURCE_FLAGS)
+variant.lib = os.path.join(vdir, f"libguardx_hip_{tag}.so")
+print(variant.build(verbose="-v" in sys.argv))
