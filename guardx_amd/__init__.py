@@ -3,5 +3,7 @@ behind the guardX `safe_rl_envs` Engine interface."""
 from .engine import Engine, ResamplingError  # noqa: F401
 from .env_config import configuration, create_env  # noqa: F401
 from .epstats import combine_episode_stats, constraint_value, episode_stats  # noqa: F401
+from . import fisher  # noqa: F401
+from .fisher import FisherOperator  # noqa: F401
 
 __version__ = "0.1.0"

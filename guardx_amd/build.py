@@ -1,5 +1,5 @@
-"""Build the project's shared libraries (MAIN, then every entry of LIBRARIES, in that order) for gfx950 in-tree with
-hipcc.
+"""Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, in that order)
+for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -215,16 +215,29 @@ LIBRARIES = {lib.key: lib for lib in (
     _side("epstats", "GXT_BUILD_ID", []),
 )}
 
+# What works on the learner's batch after collection: fisher (the TRPO family's Fisher-vector product and cg,
+# guardx_amd/fisher.py).  The same Library class, built after LIBRARIES and looked up beside it
+# (guardx_amd/_sidelib.py).  A mapping of its own only because tests/test_build_identity.py pins list(LIBRARIES) to the
+# nine libraries it records: folding the two mappings together waits for a pull request that may touch that test.
+LEARNER_LIBRARIES = {lib.key: lib for lib in (
+    _side("fisher", "GXF_BUILD_ID", _SIDE_HEADERS),
+)}
+
+
+def every_library():
+    """in build order"""
+    return [MAIN] + list(LIBRARIES.values()) + list(LEARNER_LIBRARIES.values())
+
 
 def build(force=False, verbose=False, jobs=None):
-    """Build what needs building under an inter-process lock (several ranks importing at once build once).  All nine
-    libraries; returns the path of libguardx_hip.so."""
+    """Build what needs building under an inter-process lock (several ranks importing at once build once).  Every
+    library of every_library(); returns the path of libguardx_hip.so."""
     import fcntl
     os.makedirs(LIB_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for lib in [MAIN] + list(LIBRARIES.values()):
+            for lib in every_library():
                 if force or lib.needs_build():
                     lib.build(verbose, jobs, force)
             return LIB
@@ -235,5 +248,5 @@ def build(force=False, verbose=False, jobs=None):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in LIBRARIES.values():
+    for side in every_library()[1:]:
         print(side.key, "build id", side.built_id())
