@@ -21,6 +21,7 @@ SYMBOLS = {
     "gxf_fvp": (C.c_int, [_I32, _I32, _I32, _I32, _FP, _FP, _FP, C.c_float, C.c_float, _I32, C.c_void_p, _FP, C.c_void_p]),
     "gxf_cg": (C.c_int, [_I32, _I32, _I32, _I32, _FP, _FP, _FP, C.c_float, C.c_float, _I32, _I32, C.c_void_p, _FP, _FP, _FP,
                          _FP, C.c_void_p]),
+    "gxf_tanh_act": (C.c_int, [_I32, _FP, _FP, C.c_void_p]),      # test infrastructure: the product's activation alone
 }
 
 _side = _sidelib.Binding("fisher", "gxf", SYMBOLS, GXF_OK, "fisher")

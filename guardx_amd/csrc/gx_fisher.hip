@@ -6,7 +6,8 @@
 //                  LDS holds W2, W3, the biases and their tangents (the x side), the tile of obs and its activations;
 //                  W1 and dW1 are B operands that a lane never shares (wave w owns the hidden units 16 w .. + 15), so
 //                  each lane keeps its 2 x KS1 of them in registers.  Per tile six stages, each a set of
-//                  v_mfma_f32_16x16x4_f32 chains, with a workgroup barrier (LDS only) between them:
+//                  v_mfma_f32_16x16x4_f32 chains (four interleaved ones per sum in stages 1 to 3: sum_acc), with a
+//                  workgroup barrier (LDS only) between them:
 //                    1  z1, t1 = o W1' + b1, o dW1' + db1            -> h1, dh1                      (K = pad4 D)
 //                    2  z2, t2 = h1 W2' + b2, h1 dW2' + dh1 W2' + db2 -> h2, dh2                      (K = 64)
 //                    3  dmu = h2 dW3' + dh2 W3' + db3 -> u = dmu / ((v + eps) B), 0 for rows past B   (wave w: rows 16 w ..)
@@ -54,6 +55,7 @@ constexpr int kDefaultWg = 256;  // one workgroup per CU of the MI355X: the LDS 
 constexpr int kMaxWg = 4096;
 constexpr int kMaxD = 128;
 constexpr int kCgThreads = 1024;
+constexpr int kAcc = 4;          // interleaved chains of a forward product (stages 1 to 3): see sum_acc
 
 // row stride of the obs tile: at least the 16 NT1 columns stage 6 reads, = 2 mod 32
 constexpr int nt1_of(int KS1) { return (KS1 + 3) / 4; }
@@ -76,6 +78,17 @@ struct FvpArgs {
 
 __device__ __forceinline__ mfma_f4 splat(float v) { return mfma_f4{v, v, v, v}; }
 
+// The products over a layer's inputs (z, t and dmu: K = pad4 D, 64 and 128 terms) are taken as kAcc chains, k-step s on chain
+// s mod kAcc, the bias on chain 0, added pairwise at the end.  One chain rounds 64 times at the size of its running sum;
+// four round 16 times each at half that size, which halves the error of the sum.  It shows where dmu nearly cancels: one
+// row, one tangent whose dmu is 1/50 of the sum of its terms' sizes -- 1.6e-6 of the product's norm with one chain, against
+// 2e-7 of the learners' double backward (whose BLAS sums in blocks), 3e-7 with four.
+__device__ __forceinline__ mfma_f4 sum_acc(const mfma_f4 (&a)[kAcc])
+{
+    static_assert(kAcc == 4, "pairwise over four");
+    return (a[0] + a[1]) + (a[2] + a[3]);
+}
+
 // tanh for the activations.  gx::tanh_f is 1 - 2 / (exp(2 |x|) + 1): its ABSOLUTE error is a few 1e-8 everywhere, which is
 // what a rollout needs of it, but below |x| ~ 0.6 the subtraction cancels and the relative error grows like 1e-7 / |x|
 // (0.7 % at the smallest arguments) -- and here every activation multiplies tangents and gradients, so the product is
@@ -88,8 +101,15 @@ __device__ __forceinline__ float tanh_act(float x)
     p = fmaf(z, p, -5.37397155531e-2f);
     p = fmaf(z, p, 1.33314422036e-1f);
     p = fmaf(z, p, -3.33332819422e-1f);
-    const float small = fmaf(z * x, p, x);
-    return fabsf(x) < 0.625f ? small : gx::tanh_f(x);
+    const float small = fmaf(z * x, p, x);                      // x = -0: (+0) + (-0) = +0, hence the copysignf
+    return fabsf(x) < 0.625f ? copysignf(small, x) : gx::tanh_f(x);
+}
+
+// test infrastructure (gxf_tanh_act): tanh_act by itself, one lane per element
+__global__ __launch_bounds__(kThreads) void tanh_act_kernel(int n, const float* __restrict__ x, float* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) out[i] = tanh_act(x[i]);
 }
 
 template <int KS1>
@@ -192,16 +212,22 @@ __global__ __launch_bounds__(kThreads) void fvp_kernel(FvpArgs a)
         // ---- 1
         {
             const float bz = b1[16 * w + c], bt = db1[16 * w + c];
+            // z, then its tangent: the 4 x kAcc accumulators of one of them at a time (the rows are read from LDS twice)
 #pragma unroll
-            for (int rb = 0; rb < 4; ++rb) { z[rb] = splat(bz); tt[rb] = splat(bt); }
+            for (int pass = 0; pass < 2; ++pass) {
+                mfma_f4 acc[4][kAcc];
 #pragma unroll
-            for (int s = 0; s < KS1; ++s) {
+                for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-                for (int rb = 0; rb < 4; ++rb) {
-                    const float av = O[(16 * rb + c) * SO + 4 * s + q];
-                    z[rb] = GXF_MFMA(av, w1[s], z[rb]);
-                    tt[rb] = GXF_MFMA(av, dw1[s], tt[rb]);
+                    for (int i = 0; i < kAcc; ++i) acc[rb][i] = splat(i != 0 ? 0.0f : pass == 0 ? bz : bt);
+#pragma unroll
+                for (int s = 0; s < KS1; ++s) {
+#pragma unroll
+                    for (int rb = 0; rb < 4; ++rb)
+                        acc[rb][s % kAcc] = GXF_MFMA(O[(16 * rb + c) * SO + 4 * s + q], pass == 0 ? w1[s] : dw1[s], acc[rb][s % kAcc]);
                 }
+#pragma unroll
+                for (int rb = 0; rb < 4; ++rb) (pass == 0 ? z[rb] : tt[rb]) = sum_acc(acc[rb]);
             }
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb)
@@ -217,24 +243,40 @@ __global__ __launch_bounds__(kThreads) void fvp_kernel(FvpArgs a)
         // ---- 2
         {
             const float bz = b2[16 * w + c], bt = db2[16 * w + c];
+            {                                                   // z
+                mfma_f4 acc[4][kAcc];
 #pragma unroll
-            for (int rb = 0; rb < 4; ++rb) { z[rb] = splat(bz); tt[rb] = splat(bt); }
+                for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-            for (int s = 0; s < kH / 4; ++s) {
-                const float bw = W2[(16 * w + c) * kSW + 4 * s + q], bd = dW2[(16 * w + c) * kSW + 4 * s + q];
-                float a1[4], a2[4];
+                    for (int i = 0; i < kAcc; ++i) acc[rb][i] = splat(i == 0 ? bz : 0.0f);
 #pragma unroll
-                for (int rb = 0; rb < 4; ++rb) {
-                    a1[rb] = H1[(16 * rb + c) * kSW + 4 * s + q];
-                    a2[rb] = DH1[(16 * rb + c) * kSW + 4 * s + q];
+                for (int s = 0; s < kH / 4; ++s) {
+                    const float bw = W2[(16 * w + c) * kSW + 4 * s + q];
+#pragma unroll
+                    for (int rb = 0; rb < 4; ++rb)
+                        acc[rb][s % kAcc] = GXF_MFMA(H1[(16 * rb + c) * kSW + 4 * s + q], bw, acc[rb][s % kAcc]);
                 }
 #pragma unroll
-                for (int rb = 0; rb < 4; ++rb) {
-                    z[rb] = GXF_MFMA(a1[rb], bw, z[rb]);
-                    tt[rb] = GXF_MFMA(a1[rb], bd, tt[rb]);
+                for (int rb = 0; rb < 4; ++rb) z[rb] = sum_acc(acc[rb]);
+            }
+            {                                                   // its tangent: per k-step h1 dW2', then dh1 W2'
+                mfma_f4 acc[4][kAcc];
+#pragma unroll
+                for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+                    for (int i = 0; i < kAcc; ++i) acc[rb][i] = splat(i == 0 ? bt : 0.0f);
+#pragma unroll
+                for (int s = 0; s < kH / 4; ++s) {
+                    const float bw = W2[(16 * w + c) * kSW + 4 * s + q], bd = dW2[(16 * w + c) * kSW + 4 * s + q];
+#pragma unroll
+                    for (int rb = 0; rb < 4; ++rb)
+                        acc[rb][s % kAcc] = GXF_MFMA(H1[(16 * rb + c) * kSW + 4 * s + q], bd, acc[rb][s % kAcc]);
+#pragma unroll
+                    for (int rb = 0; rb < 4; ++rb)
+                        acc[rb][s % kAcc] = GXF_MFMA(DH1[(16 * rb + c) * kSW + 4 * s + q], bw, acc[rb][s % kAcc]);
                 }
 #pragma unroll
-                for (int rb = 0; rb < 4; ++rb) tt[rb] = GXF_MFMA(a2[rb], bw, tt[rb]);
+                for (int rb = 0; rb < 4; ++rb) tt[rb] = sum_acc(acc[rb]);
             }
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb)
@@ -249,12 +291,15 @@ __global__ __launch_bounds__(kThreads) void fvp_kernel(FvpArgs a)
         wg_sync_lds();
         // ---- 3: this wave's 16 rows
         {
-            mfma_f4 m0 = splat(db3[c]), m1 = splat(0.0f);
+            mfma_f4 m0a[kAcc], m1a[kAcc];
+#pragma unroll
+            for (int i = 0; i < kAcc; ++i) { m0a[i] = splat(i == 0 ? db3[c] : 0.0f); m1a[i] = splat(0.0f); }
 #pragma unroll
             for (int s = 0; s < kH / 4; ++s) {
-                m0 = GXF_MFMA(H2[(16 * w + c) * kSW + 4 * s + q], dW3[c * kSW + 4 * s + q], m0);
-                m1 = GXF_MFMA(DH2[(16 * w + c) * kSW + 4 * s + q], W3[c * kSW + 4 * s + q], m1);
+                m0a[s % kAcc] = GXF_MFMA(H2[(16 * w + c) * kSW + 4 * s + q], dW3[c * kSW + 4 * s + q], m0a[s % kAcc]);
+                m1a[s % kAcc] = GXF_MFMA(DH2[(16 * w + c) * kSW + 4 * s + q], W3[c * kSW + 4 * s + q], m1a[s % kAcc]);
             }
+            const mfma_f4 m0 = sum_acc(m0a), m1 = sum_acc(m1a);
             const float iv = inv[c];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -569,6 +614,16 @@ extern "C" int64_t gxf_work_bytes(int32_t B, int32_t D, int32_t A, int32_t workg
 {
     if (check_shape("gxf_work_bytes", B, D, A, kH, workgroups) != GXF_OK) return -1;
     return work_bytes(param_count(D, A, kH), workgroups ? workgroups : default_workgroups(B));
+}
+
+extern "C" gxf_status gxf_tanh_act(int32_t n, const float* d_x, float* d_out, void* stream)
+{
+    if (!d_x || !d_out) return fail(GXF_ERR_ARG, "gxf_tanh_act: null pointer");
+    if (n < 0) return fail(GXF_ERR_ARG, "gxf_tanh_act: negative n");
+    if (n == 0) return GXF_OK;
+    const unsigned blocks = (unsigned)(((int64_t)n + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(tanh_act_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, n, d_x, d_out);
+    return launched("gxf_tanh_act");
 }
 
 extern "C" gxf_status gxf_fvp(int32_t B, int32_t D, int32_t A, int32_t hidden, const float* d_obs, const float* d_theta,

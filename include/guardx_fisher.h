@@ -21,7 +21,9 @@
  *   gz1  = (W2' gz2)(1 - h1^2)   gW1 += gz1 o'     gb1 += gz1
  *   y_ls = c dls,  c = v (-4 v / (v + eps)^2 + 8 v^2 / (v + eps)^3) / 2
  * and y += damping x.  Every product of a 64-row tile of obs is a chain of v_mfma_f32_16x16x4_f32
- * (float32, one fused multiply-add per term); a workgroup adds its tiles' sums in tile order and
+ * (float32, one fused multiply-add per term; the sums over a layer's inputs -- z, their tangents
+ * and dmu -- as four chains, k-step s on chain s mod 4 and the bias on chain 0, added as
+ * (c0 + c1) + (c2 + c3)); a workgroup adds its tiles' sums in tile order and
  * writes one partial vector, the partial vectors are added in workgroup order.  No atomics: two
  * calls with the same arguments give the same bits.  1 / ((v + eps) B) and c are evaluated in
  * float64 and rounded once.
@@ -41,7 +43,7 @@ extern "C" {
 
 typedef enum gxf_status {
     GXF_OK = 0,
-    GXF_ERR_ARG = 1,         /* null pointer, B < 1, D < 1, A < 1, iters < 0, workgroups outside 0 .. 4096 */
+    GXF_ERR_ARG = 1,         /* null pointer, B < 1, D < 1, A < 1, iters < 0, n < 0, workgroups outside 0 .. 4096 */
     GXF_ERR_UNSUPPORTED = 2, /* hidden != 64, D > 128, A odd or > 16 */
     GXF_ERR_HIP = 4          /* a HIP runtime call failed */
 } gxf_status;
@@ -79,6 +81,12 @@ gxf_status gxf_fvp(int32_t B, int32_t D, int32_t A, int32_t hidden, const float*
 gxf_status gxf_cg(int32_t B, int32_t D, int32_t A, int32_t hidden, const float* d_obs, const float* d_theta,
                   const float* d_g, float eps, float damping, int32_t iters, int32_t workgroups, void* d_work,
                   float* d_xhat, float* d_s, float* d_rdot, int32_t* d_iters, void* stream);
+
+/* Test infrastructure, like `workgroups`: d_out[i] = the activation the product applies to d_x[i], i < n
+ * (the kernel's own tanh: an odd polynomial below |x| = 0.625, the rollouts' tanh above), so that
+ * the tests can measure it by itself.  n < 0 and a null pointer are refused, n == 0 launches nothing.
+ * One launch. */
+gxf_status gxf_tanh_act(int32_t n, const float* d_x, float* d_out, void* stream);
 
 #ifdef __cplusplus
 }

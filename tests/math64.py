@@ -182,6 +182,82 @@ def tanh_set():
                                   SPECIALS]))
 
 
+# tanh_act (gx_fisher.hip, the Fisher product's activation; libguardx_fisher.so:gxf_tanh_act): an odd polynomial below
+# |x| = 0.625, tanh_f from there on.  Its bound is the figure its source states, in ulp of the result.
+TANH_ACT_SPLIT, TANH_ACT_SAT, TANH_ACT_TOP = F32(0.625), F32(9.0), F32(16.0)
+TANH_ACT_STRIDE, TANH_ACT_NEAR = 256, 4096
+TANH_ACT_BOUND_ULP = 2.3
+_TANH_ACT_SET = None
+
+
+def tanh_act_set():
+    """every 256th bit pattern of the positive normal floats below 16 and every pattern within 4096 of 0.625 and of 9,
+    with their negatives, and SPECIALS (larger than MAX_SET, so not one of all_sets(); built once, read-only)"""
+    global _TANH_ACT_SET
+    if _TANH_ACT_SET is None:
+        lo, hi = int(f2u(FLT_MIN)[0]), int(f2u(TANH_ACT_TOP)[0])
+        near = [np.arange(int(f2u(p)[0]) - TANH_ACT_NEAR, int(f2u(p)[0]) + TANH_ACT_NEAR + 1, dtype=np.int64)
+                for p in (TANH_ACT_SPLIT, TANH_ACT_SAT)]
+        pos = u2f(np.concatenate([np.arange(lo, hi, TANH_ACT_STRIDE, dtype=np.int64)] + near).astype(U32))
+        _TANH_ACT_SET = np.concatenate([both_signs(pos), SPECIALS])
+        _TANH_ACT_SET.setflags(write=False)
+    return _TANH_ACT_SET
+
+
+def tanh_act32(x, tanh_f):
+    """tanh_act in numpy float32, each fmaf taken through float64 (the product of two float32 is exact there); `tanh_f`:
+    the float32 tanh_f it hands |x| >= 0.625 to (the C checker's twin)"""
+    x = np.asarray(x, F32)
+    d = np.float64
+    with np.errstate(all="ignore"):
+        fma = lambda a, b, c: (np.asarray(a, F32).astype(d) * np.asarray(b, F32).astype(d) + np.asarray(c, F32).astype(d)).astype(F32)  # noqa: E731
+        z = x * x
+        p = fma(z, F32(-5.70498872745e-3), F32(2.06390887954e-2))
+        p = fma(z, p, F32(-5.37397155531e-2))
+        p = fma(z, p, F32(1.33314422036e-1))
+        p = fma(z, p, F32(-3.33332819422e-1))
+        small = np.copysign(fma(z * x, p, x), x)
+        assert z.dtype == F32 and small.dtype == F32
+        return np.where(np.abs(x) < TANH_ACT_SPLIT, small, np.asarray(tanh_f(x), F32))
+
+
+def check_tanh_act(x, y, who):
+    """what tests/test_math64.py (the restatement) and tests/test_gpu_fisher.py (the device) both ask of y = tanh_act(x)
+    over tanh_act_set(); prints and returns the worst error of each branch in ulp of the result"""
+    x, y = np.asarray(x, F32), np.asarray(y, F32)
+    assert x.shape == y.shape and y.dtype == F32
+    nan = np.isnan(x)
+    assert nan.sum() >= 1 and np.isnan(y[nan]).all() and not np.isnan(y[~nan]).any()            # NaN in, NaN out, only there
+    assert (y[x == np.inf] == 1).all() and (y[x == -np.inf] == -1).all() and np.isinf(x).sum() >= 2
+    zero = x == 0
+    assert zero.sum() >= 2 and (f2u(y[zero]) == f2u(x[zero])).all(), "+-0 keeps its sign"
+    den = (x != 0) & (np.abs(x) < FLT_MIN)
+    assert den.sum() >= 4 and (f2u(y[den]) == f2u(x[den])).all(), "denormals are kept: tanh_act(x) = x there"
+    # odd: the set holds -x for every x
+    ub, first = np.unique(f2u(x[~nan]), return_index=True)
+    yb = f2u(y[~nan])[first]
+    neg = ub ^ U32(0x80000000)
+    at = np.searchsorted(ub, neg)
+    assert (ub[at] == neg).all()
+    assert (yb[at] == yb ^ U32(0x80000000)).all(), "tanh_act(-x) = -tanh_act(x), bit for bit"
+    assert (np.abs(y[~nan]) <= 1).all()
+    fin = np.isfinite(x)                                       # (+-inf and NaN: exact, above)
+    x, y = x[fin], y[fin]
+    ref = ref_tanh(x)
+    ulp = ulp_err(y, ref)
+    ax = np.abs(x)
+    out = {}
+    for name, sel in (("below 0.625", ax < TANH_ACT_SPLIT), ("0.625 and above", ax >= TANH_ACT_SPLIT)):
+        i = np.flatnonzero(sel)[np.argmax(ulp[sel])]
+        out[name] = float(ulp[i])
+        print("%s tanh_act %-16s worst %.3f ulp at x = %r (%08x): got %r, float64 %r; bound %.1f, %d inputs"
+              % (who, name, ulp[i], float(x[i]), f2u(x[i:i + 1])[0], float(y[i]), float(ref[i]), TANH_ACT_BOUND_ULP, sel.sum()))
+    assert ulp.max() <= TANH_ACT_BOUND_ULP, out
+    big = ax >= TANH_ACT_SPLIT
+    assert abs_err(y[big], ref[big]).max() <= BOUNDS["tanh"]                                   # tanh_f's own bound
+    return out
+
+
 RCP_EXPS = range(-149, 128)
 
 

@@ -19,7 +19,7 @@ from guardx_amd import build, fisher
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY, PREFIX = "fisher", "gxf"
 LIB = build.LEARNER_LIBRARIES[KEY]
-PROTOS = 7
+PROTOS = 8
 
 
 def _norm(name):
@@ -168,6 +168,9 @@ def test_arg_errors_fire_before_a_launch(defined):
     for kw in (dict(obs=None), dict(theta=None), dict(g=None), dict(work=None), dict(xh=None), dict(s=None), dict(rd=None),
                dict(it=None), dict(iters=-1), dict(B=0), dict(D=0), dict(A=0), dict(wg=-1), dict(wg=4097)):
         assert _cg(lib, **kw) == n.GXF_ERR_ARG, kw
+    for args in ((-1, PTR, 2 * PTR), (4, None, 2 * PTR), (4, PTR, None)):
+        assert lib.gxf_tanh_act(*args, None) == n.GXF_ERR_ARG, args
+        assert b"gxf_tanh_act" in lib.gxf_last_error()
     with pytest.raises(n.GxfError, match="guardx fisher status 1: gxf_fvp: null pointer") as e:
         n.check(_fvp(lib, obs=None))
     assert e.value.status == n.GXF_ERR_ARG
