@@ -1,7 +1,8 @@
 // gx_usl.hip -- libguardx_usl.so (include/guardx_usl.h): `ac.step(o)` of the USL learner (safe_rl_libX/usl/usl.py:478-553,
 // usl_core.py:146-196, 239-248) for one control step over all envs: the actor's mu_net and the critic v on the observation
 // row, the cost critic Q(obs, act) = Softplus(c_net(cat(obs, act))) on the sampled action, and the learner's correction:
-// up to niter passes of a = a - eta s / (max |s| + 1e-8), s the scaled gradient of Q with respect to the action.
+// up to niter passes of a = a - eta acc / (max |acc| + 1e-8), acc the running sum over the passes so far of s, the scaled
+// gradient of Q with respect to the action (the reference never clears act.grad).
 //
 // The networks' arithmetic is the fused rollout's (gx_policy.h) and the checker's (oracle/gx_oracle.c:mlp_forward): every
 // hidden unit is one v_mfma_f32_16x16x4_f32 chain over k ascending, started from its bias (that instruction accumulates
@@ -60,6 +61,26 @@ struct ProbeArgs {
 // per row, what the iteration returns
 struct RowOut { float q0; int iters, stop; };
 
+// One row's update on AA action components.  act.grad is never cleared between the reference's passes
+// (usl_core.py:180-194), so the step uses acc, the running sum of the passes' scaled gradients s = c g: the first pass
+// sets it (the first backward() sets act.grad), the later ones add to it.  g0 (may be null): where s itself goes.
+template <int AA>
+GX_D void q_update(float (&acc)[kMaxA], float* a, const float* g, float c, float eta, bool first, float* g0)
+{
+    float Z = 0.0f;
+#pragma unroll
+    for (int k = 0; k < AA; ++k) {
+        const float s = __fmul_rn(c, g[k]);
+        if (g0) g0[k] = s;
+        acc[k] = first ? s : __fadd_rn(acc[k], s);
+        const float m = fabsf(acc[k]);
+        Z = (k == 0 || m > Z) ? m : Z;
+    }
+    const float den = __fadd_rn(Z, 1e-8f);
+#pragma unroll
+    for (int k = 0; k < AA; ++k) a[k] = __fsub_rn(a[k], __fmul_rn(eta, __fdiv_rn(acc[k], den)));
+}
+
 // The iteration of include/guardx_usl.h on the 16 rows of the workgroup.  On entry (after a barrier): the rows' actions in
 // lds[L.act], P = the first layer's pre-activation over the observation columns, c_net's parts staged.  On exit (after a
 // barrier): the final actions in lds[L.act]; the threads tid < 16 hold their row's result.  rows = valid rows;
@@ -77,6 +98,9 @@ GX_D RowOut q_iterate(float* lds, const QLds& L, float* H1, float* H2, const QAr
     q_load_wa<HC>(wa, q, tid);
     RowOut ro;
     ro.q0 = 0.0f; ro.iters = 0; ro.stop = tid < rows ? -1 : 3;
+    float acc[kMaxA]; // the row's running sum of s over its passes
+#pragma unroll
+    for (int k = 0; k < kMaxA; ++k) acc[k] = 0.0f;
 
     for (int pass = 0;; ++pass) {
         q_pass<HC, true>(lds, L, H1, H2, q, wa, npass > 0, tid);
@@ -96,13 +120,16 @@ GX_D RowOut q_iterate(float* lds, const QLds& L, float* H1, float* H2, const QAr
                 else {
                     const float c = __fmul_rn(q.gscale, softplus_grad_f(z));
                     const float* g = gt + tid * kAS;
-                    float Z = fabsf(__fmul_rn(c, g[0]));
-                    for (int k = 1; k < A; ++k) { const float s = fabsf(__fmul_rn(c, g[k])); Z = s > Z ? s : Z; }
-                    const float den = __fadd_rn(Z, 1e-8f);
-                    for (int k = 0; k < A; ++k) {
-                        const float s = __fmul_rn(c, g[k]);
-                        if (pass == 0 && grad0) grad0[(size_t)tid * A + k] = s;
-                        a[k] = __fsub_rn(a[k], __fmul_rn(q.eta, __fdiv_rn(s, den)));
+                    float* g0 = pass == 0 && grad0 ? grad0 + (size_t)tid * A : nullptr;
+                    switch (A) { // even, 2 .. kMaxA (gx_step.h:shape_ok): every form indexes acc statically
+                    case 2: q_update<2>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    case 4: q_update<4>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    case 6: q_update<6>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    case 8: q_update<8>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    case 10: q_update<10>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    case 12: q_update<12>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    case 14: q_update<14>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
+                    default: q_update<16>(acc, a, g, c, q.eta, ro.iters == 0, g0); break;
                     }
                     moved = true;
                     ro.iters += 1;

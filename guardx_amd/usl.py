@@ -3,17 +3,20 @@ C_Critic of usl_core.py:146-196, 239-248 evaluated there).
 
 The learner evaluates a cost critic Q(obs, act) = Softplus(c_net(cat(obs, act))) next to ac.step and, after its warm-up,
 walks the action down Q's gradient before env.step sees it: up to niter passes of
-a = a - eta s / (max |s| + 1e-8), s = grad_scale dQ/da, while max a <= 1 and Q > delta.  Per control step: one
+a = a - eta acc / (max |acc| + 1e-8), acc the running sum of the passes' s = grad_scale dQ/da, while max a <= 1 and
+Q > delta.  Per control step: one
 `gxu_policy_step` launch (libguardx_usl.so, include/guardx_usl.h: ac.step, Q on the sampled action, the iteration with
 its forward and backward passes on the MFMA chains) and one `gx_step_slab` launch on act_safe[t] (env.step with the
 speculated reset_done, committed on the host) -- the two launches per control step the step-wise rollout_policy already
 has.  Everything runs on torch's current stream; nothing synchronises.
 
-Two quirks of the reference, kept in the open (include/guardx_usl.h):
+Three quirks of the reference, kept in the open (include/guardx_usl.h):
   * usl_core.py:184 backpropagates pred.mean(), so its gradient is the true one divided by the batch size; the division
     by max |s| takes the factor out again except against the 1e-8.  grad_scale=None means 1 / env_num, the reference's
     arithmetic for an unsharded engine; grad_scale=1.0 is the unscaled form.
   * usl_core.py:174-175 tests the SIGNED maximum, max_k a[k] > 1, not |a|: a component below -1 does not stop a row.
+  * usl_core.py:180-194 never clears act.grad, so every backward() adds to it: the step of pass p follows the sum of the
+    scaled gradients of the passes 1 .. p, not the gradient at the current action.
 """
 import ctypes as C
 

@@ -13,19 +13,25 @@
  *   tail (t == T): the prologue for step T - 1, then obs_last, val_last; no action, no noise, no Q.
  *
  * The iteration, per row (usl_core.py:165-196):
- *   a = act
+ *   a = act;  acc = 0
  *   repeat at most niter times:
  *       if max_k a[k] > 1:  stop (reason 1)        the SIGNED maximum, not |a|: usl_core.py:174-175 as written
  *       q = Q(obs, a);  if q <= delta: stop (reason 2)
  *       g~[k] = d z3 / d a[k]                       z3 = c_net's output before its Softplus
  *       c = grad_scale * softplus'(z3)              softplus'(z) = z > 20 ? 1 : e^z / (e^z + 1)  (torch's backward)
- *       s[k] = c g~[k];  Z = max_k |s[k]|;  a[k] = a[k] - eta * (s[k] / (Z + 1e-8))
+ *       s[k] = c g~[k];  acc[k] = acc[k] + s[k];  Z = max_k |acc[k]|;  a[k] = a[k] - eta * (acc[k] / (Z + 1e-8))
  *   reason 0: niter updates applied.  There is no clamp, and a stopped row never moves again.
- * Two quirks of the reference, kept in the open rather than copied silently:
+ * Three quirks of the reference, kept in the open rather than copied silently:
  *   * usl_core.py:184 backpropagates pred.mean(), so its act.grad is the true gradient divided by the batch size; the
  *     division by Z takes the factor out again except against the 1e-8.  grad_scale carries it: 1 / env_num is the
  *     reference's arithmetic for an unsharded engine, 1 the unscaled form.
  *   * the box test is max_k a[k] > 1 on the signed components: a row at a = (-3, 0.5) keeps iterating.
+ *   * usl_core.py:180-194 never clears act.grad: c_net.zero_grad() (line 182) zeroes the network's gradients only and
+ *     act is the same leaf tensor in every pass, so each backward() (line 184) ADDS to act.grad (an fp32 add inside
+ *     torch's accumulation) and the update of pass p (lines 190-194) uses the sum of s over the passes 1 .. p, a
+ *     momentum-like step, not the gradient at the current action.  Against the memoryless form (which this library
+ *     computed before): equal on rows that move once, 8.9e-4 apart on rows that move twice, up to 0.05 at ten passes
+ *     and 0.54 at twenty (C_Critic(43, 2, (64, 64)), 64 rows, eta 0.05); no stop reason changed.
  *
  * Arithmetic.  Hidden units are the project's chains (guardx_amd/csrc/gx_policy.h, oracle/gx_oracle.c:mlp_forward):
  *   hidden unit j:  acc = b[j]; acc = fmaf(x[k], W[j][k], acc) for k = 0, 1, ...; then gx tanh
@@ -39,10 +45,11 @@
  *   g1[k] = (1 - h1[k] * h1[k]) * d1[k]
  *   g~[i] = dot16(W1[:, D + i], g1)                                                 (the order of dot16 over k)
  *   e = exp(z3);  sp = z3 > 20 ? 1 : e / (e + 1);  c = grad_scale * sp
- *   s[i] = c * g~[i];  Z = |s[0]|, then Z = |s[i]| > Z ? |s[i]| : Z for i = 1 .. A - 1;  den = Z + 1e-8f
- *   a[i] = a[i] - eta * (s[i] / den)                       (IEEE division, then the product, then the difference)
- * A numpy float32 transcription of the last three lines gives the same bits from the same s.  (torch evaluates
- * eta * s / den from the left, (eta s) / den: a last-place difference, not a different update.)
+ *   s[i] = c * g~[i];  acc[i] = s[i] in the row's first pass, acc[i] + s[i] after it (per row, in registers)
+ *   Z = |acc[0]|, then Z = |acc[i]| > Z ? |acc[i]| : Z for i = 1 .. A - 1;  den = Z + 1e-8f
+ *   a[i] = a[i] - eta * (acc[i] / den)                     (IEEE division, then the product, then the difference)
+ * A numpy float32 transcription of the last three lines gives the same bits from the same acc.  (torch evaluates
+ * eta * acc / den from the left, (eta acc) / den: a last-place difference, not a different update.)
  *
  * Parameters: d_params = pack_actor_critic layout on D inputs (gxu_params_floats);
  * d_c_params = c_net W1[hc][D + A] b1 W2[hc][hc] b2 W3[1][hc] b3 (gxu_q_floats); h, hc in {64, 128, 192, 256},
@@ -169,9 +176,9 @@ gxu_status guardx_usl_tail_probe(int32_t n, int32_t D, int32_t A, int32_t hidden
 
 /* The iteration alone, with the step kernel's own device functions, on n caller-supplied rows d_obs [n][D], d_act
  * [n][A]:  d_a_safe [n][A] the final a;  d_q0 [n] Q at the input action;  d_grad0 [n][A] the scaled gradient s of the
- * first pass, 0 for a row that stops before it;  d_iters [n] (int32) the updates applied;  d_stop [n] (int32) why the
- * row stopped: 0 niter exhausted, 1 max a > 1, 2 q <= delta.  d_work: gxu_probe_work_floats floats of scratch, filled
- * by this call itself (stream-ordered). */
+ * first pass (s, not the running sum: with niter = 1 the two are the same), 0 for a row that stops before it;
+ * d_iters [n] (int32) the updates applied;  d_stop [n] (int32) why the row stopped: 0 niter exhausted, 1 max a > 1,
+ * 2 q <= delta.  d_work: gxu_probe_work_floats floats of scratch, filled by this call itself (stream-ordered). */
 gxu_status gxu_correction_probe(int32_t n, int32_t D, int32_t A, int32_t c_hidden, const float* d_c_params,
                                 float* d_work, const float* d_obs, const float* d_act, float delta, int32_t niter,
                                 float eta, float grad_scale, float* d_a_safe, float* d_q0, float* d_grad0,

@@ -9,7 +9,7 @@ IDS = {
     "critic": "1afdcabad09cc0d419a8d9a5",
     "statewise": "e6d760b1dbf2d5195c1247e0",
     "safelayer": "de39af70500c88f6609d39c8",
-    "usl": "34485803dc952d5454f49150",
+    "usl": "1175e0847c1bddf1d90b8286",
     "lpg": "e196100c68b94afce543fb6f",
     "episode": "2ac1225ff7d697761c70297a",
     "mathprobe": "1500249652e842aae76b306b",

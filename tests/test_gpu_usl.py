@@ -1,7 +1,8 @@
 """Engine.rollout_usl (the USL learner's collection loop on the device, guardx_amd/usl.py, libguardx_usl.so): bit equality
-with rollout_policy in the warm-up branch, the iteration as a pure map, the rollout against the probe and against a
-second engine driven by act_safe, the update against its numpy float32 transcription, one pass against the float64
-restatement (tests/usl64.py, where the bounds are derived), the noise counter, errors and the batch helper.
+with rollout_policy in the warm-up branch, the iteration against a host loop that carries the running sum of the
+passes' gradients and, pass by pass, against float64, the rollout against the probe and against a second engine driven
+by act_safe, the update against its numpy float32 transcription, one pass against the float64 restatement
+(tests/usl64.py, where the bounds are derived), the noise counter, errors and the batch helper.
 
 Largest err / bound per output of test_single_pass_against_float64 are printed by the test (pytest -s) and recorded in
 INTEGRATION.md.  Edge rows (tests/usl64.py) may differ in `stop` only and are at most 2 % of every case
@@ -152,28 +153,145 @@ def test_warmup_bit_equal_on_the_thread_per_env_path():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 2. the iteration is a pure map
+# 2. the iteration carries the running sum of its passes' gradients (usl_core.py:180-194: act.grad is never cleared)
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["point64", "ant256", "walker128", "saturated192"])
-def test_iteration_is_a_pure_map(name):
-    """correction_probe(niter = k) equals correction_probe(niter = 1) applied k times by the host, feeding a_safe back:
-    a_safe bit for bit and iters summed, for k = 2, 5, 20; a stopped row is a fixed point"""
+MULTI_CASES = ["point64", "ant256", "walker128", "saturated192"]
+MULTI_ROWS = (1, 15, 16, 17, 33)                  # 16 rows per workgroup
+MULTI_SCALES = (1.0, 1.0 / 2000)
+MULTI_PASSES = 20
+# Rows MULTI_ROW0[case] .. of probe_inputs: with 33 rows or fewer the 2 % cap on edge rows allows none, and over 20 passes
+# float64 finds one to three in most windows of 33 rows (q within dq of delta at some pass).  Each case starts at the first
+# row (for ant256 the window used so far) from which float64 finds no edge row in 33 rows at either scale, whose first row
+# runs all 20 passes -- so that n = 1 carries a running sum too -- and whose first 15 rows hold a row that never moves
+# (tests/test_usl_host.py::test_multi_pass_inputs_are_sized)
+MULTI_ROW0 = {"point64": 34, "ant256": 99, "walker128": 45, "saturated192": 14}
+_host_loops = {}
+
+
+def host_loop(name, n, gs):
+    """The iteration on n rows of a case (from MULTI_ROW0[case]), driven by the host from niter = 1 probes, computed once per (case, n,
+    grad_scale) and shared: at each pass the probe's grad0 at the current a is added in float32 to the host's acc (the
+    first pass's grad0 IS acc), the step is usl64.update32(a, acc, eta), a stopped row stays where it is.  -> (qp, obs,
+    act, delta, passes); passes[p - 1] = dict(a_in, grad0, stop1 (the niter = 1 probe's stop at a_in), live (rows that
+    moved in pass p), a, iters, stop (the state after p passes: what correction_probe(niter = p) has to return))"""
+    key = (name, n, gs)
+    if key not in _host_loops:
+        from guardx_amd import Engine
+        qm, obs, act, delta = probe_inputs(name)
+        r0 = MULTI_ROW0[name]
+        obs, act = obs[r0:r0 + n], act[r0:r0 + n]
+        qp = Engine.pack_q_critic(qm, device='cuda')
+        _host_loops[key] = (qm, qp, obs, act, delta, _drive_passes(qp, obs, act, delta, gs, MULTI_PASSES))
+    return _host_loops[key]
+
+
+def _drive_passes(qp, obs, act, delta, gs, npasses):
+    """host_loop's passes on given rows"""
+    n = len(act)
+    a, acc = act.copy(), None
+    iters, stop, passes = np.zeros(n, np.int64), np.zeros(n, np.int64), []
+    for p in range(1, npasses + 1):
+        r = _probe(qp, obs, a, delta=delta, niter=1, eta=ETA, grad_scale=gs)
+        fixed = r['stop'] != 0
+        np.testing.assert_array_equal(bits(r['a_safe'][fixed]), bits(a[fixed]))      # a stopped row is a fixed point
+        assert (r['iters'][fixed] == 0).all() and (r['iters'][~fixed] == 1).all()
+        assert (r['stop'][stop != 0] == stop[stop != 0]).all()                       # and stops for the same reason
+        stop = np.where(stop == 0, r['stop'], stop)
+        live = stop == 0
+        acc = r['grad0'].copy() if acc is None else (acc + r['grad0']).astype(F)
+        a_in, a = a, np.where(live[:, None], usl64.update32(a, acc, ETA), a).astype(F)
+        iters = iters + live
+        passes.append(dict(a_in=a_in, grad0=r['grad0'].copy(), stop1=r['stop'].copy(), live=live, a=a.copy(),
+                           iters=iters.copy(), stop=stop.copy()))
+    return passes
+
+
+@pytest.mark.parametrize("gs", MULTI_SCALES)
+@pytest.mark.parametrize("n", MULTI_ROWS)
+@pytest.mark.parametrize("name", MULTI_CASES)
+def test_iteration_accumulates_the_gradient(name, n, gs):
+    """correction_probe(niter = k) equals the host loop of host_loop() after k passes for k = 2, 3, 5, 20: a_safe bit for
+    bit, iters and stop equal.  (The memoryless iteration -- niter = 1 applied k times, feeding a_safe back -- which the
+    library computed before, differs from it on every row that moves twice.)"""
+    qm, qp, obs, act, delta, passes = host_loop(name, n, gs)
+    for k in (2, 3, 5, 20):
+        r = _probe(qp, obs, act, delta=delta, niter=k, eta=ETA, grad_scale=gs)
+        w = passes[k - 1]
+        np.testing.assert_array_equal(bits(r['a_safe']), bits(w['a']), err_msg=f"{name} n={n} k={k}")
+        np.testing.assert_array_equal(r['iters'], w['iters'], err_msg=f"{name} n={n} k={k}")
+        np.testing.assert_array_equal(r['stop'], w['stop'], err_msg=f"{name} n={n} k={k}")
+        np.testing.assert_array_equal(bits(r['grad0']), bits(passes[0]['grad0']), err_msg=f"{name} n={n} k={k}")
+    assert r['iters'][0] == MULTI_PASSES and passes[1]['live'][0]      # at every n the first row carries a running sum
+    if n == 33:
+        # the sizing of tests/test_usl_host.py::test_multi_pass_inputs_are_sized: rows that run all 20 passes, rows that
+        # stop, and the running sum matters (some row moves twice or more and its second step is not the memoryless one)
+        assert r['iters'].max() == MULTI_PASSES and len(set(np.unique(r['stop']))) >= 2
+        twice = passes[1]['live']
+        memoryless = usl64.update32(passes[1]['a_in'], passes[1]['grad0'], ETA)
+        assert twice.any() and (bits(memoryless[twice]) != bits(passes[1]['a'][twice])).any()
+
+
+@pytest.mark.parametrize("A", [2, 4, 6, 8, 10, 12, 14, 16])
+def test_accumulation_at_every_action_width(A):
+    """the row update is compiled once per action width (gx_usl.hip:q_update<A>): every width against the host loop,
+    niter = 1 .. 6 bit for bit, on 17 rows of a 64-wide c_net with delta at the median of q0"""
     from guardx_amd import Engine
-    qm, obs, act, delta = probe_inputs(name)
+    n, D = 17, 43
+    qm = make_q(D, A, 64, 80 + A)
+    rng = np.random.default_rng(300 + A)
+    obs = rng.normal(size=(n, D)).astype(F)
+    act = (rng.normal(size=(n, A)) * 0.4 / math.sqrt(A / 2)).astype(F)
+    delta = float(F(np.median(usl64.QCritic(qm).forward(obs, act)['q'])))
     qp = Engine.pack_q_critic(qm, device='cuda')
-    a, iters, seq = act.copy(), np.zeros(len(act), np.int64), {}
-    for k in range(1, 21):
-        r = _probe(qp, obs, a, delta=delta, niter=1, eta=ETA)
-        stopped = r['stop'] != 0
-        np.testing.assert_array_equal(bits(r['a_safe'][stopped]), bits(a[stopped]))      # a fixed point
-        assert (r['iters'][stopped] == 0).all() and (r['iters'][~stopped] == 1).all()
-        a, iters = r['a_safe'], iters + r['iters']
-        seq[k] = (a.copy(), iters.copy())
-    for k in (2, 5, 20):
-        r = _probe(qp, obs, act, delta=delta, niter=k, eta=ETA)
-        np.testing.assert_array_equal(bits(r['a_safe']), bits(seq[k][0]), err_msg=f"{name} k={k}")
-        np.testing.assert_array_equal(r['iters'], seq[k][1], err_msg=f"{name} k={k}")
-    assert len(set(np.unique(r['stop']))) >= 2 and r['iters'].max() == 20
+    passes = _drive_passes(qp, obs, act, delta, 1.0 / n, 6)
+    for k in range(1, 7):
+        r = _probe(qp, obs, act, delta=delta, niter=k, eta=ETA, grad_scale=1.0 / n)
+        w = passes[k - 1]
+        np.testing.assert_array_equal(bits(r['a_safe']), bits(w['a']), err_msg=f"A={A} k={k}")
+        np.testing.assert_array_equal(r['iters'], w['iters'], err_msg=f"A={A} k={k}")
+        np.testing.assert_array_equal(r['stop'], w['stop'], err_msg=f"A={A} k={k}")
+    assert r['iters'].max() >= 3 and (r['iters'] == 0).any()          # rows that carry a sum, rows that never move
+    assert np.isfinite(r['a_safe']).all()
+
+
+@pytest.mark.parametrize("gs", MULTI_SCALES)
+@pytest.mark.parametrize("n", MULTI_ROWS)
+@pytest.mark.parametrize("name", MULTI_CASES)
+def test_multi_pass_against_float64(name, n, gs):
+    """Pass by pass over the 20 passes: from the device's own action before the pass (correction_probe(niter = p - 1)'s
+    a_safe) and the float64 sum of the device's own grad0s of the passes before it, correction_probe(niter = p)'s a_safe
+    lies within usl64.one_pass's bound of the float64 step, and its stop equals float64's, on the rows that have not been
+    edge rows so far; edge rows are at most 2 % of the rows."""
+    qm, qp, obs, act, delta, passes = host_loop(name, n, gs)
+    Q = usl64.QCritic(qm)
+    acc, dacc = None, None
+    ok, stopped = np.ones(n, bool), np.zeros(n, bool)
+    a_dev, worst = act, 0.0
+    for p in range(1, MULTI_PASSES + 1):
+        r = _probe(qp, obs, act, delta=delta, niter=p, eta=ETA, grad_scale=gs)
+        w = Q.one_pass(obs, a_dev, delta, ETA, gs, acc=acc, dacc=dacc)
+        ok &= stopped | ~w['edge']
+        rows = ok & ~stopped
+        moved = rows & (w['stop'] < 0)
+        np.testing.assert_array_equal(r['stop'][rows], np.where(w['stop'][rows] < 0, 0, w['stop'][rows]), err_msg=f"pass {p}")
+        np.testing.assert_array_equal(bits(r['a_safe'][rows & ~moved]), bits(a_dev[rows & ~moved]), err_msg=f"pass {p}")
+        err = np.abs(r['a_safe'] - w['a_next'])[moved]
+        if moved.any():
+            with np.errstate(divide='ignore', invalid='ignore'):
+                worst = max(worst, float(np.where(err == 0, 0.0, err / w['da_next'][moved]).max()))
+        stopped |= w['stop'] > 0
+        # the float64 sum of the device's own grad0s at the device's own actions, and what the device's fp32 sum may be off
+        g = passes[p - 1]['grad0'].astype(np.float64)
+        np.testing.assert_array_equal(bits(passes[p - 1]['a_in'][rows]), bits(a_dev[rows]))
+        acc = g if acc is None else acc + g
+        dacc = np.zeros_like(g) if dacc is None else dacc + usl64.MARGIN * usl64.U * np.abs(acc)
+        a_dev = r['a_safe']
+    share = float((~ok).mean())
+    print(f"usl multi pass {name} n={n} gs={gs:g}: edge rows {share:.4f}  a_safe err / bound {worst:.3f}  "
+          f"rows at 20 passes {int((r['iters'] == MULTI_PASSES).sum())}")
+    assert share <= EDGE_CAP, share
+    assert np.isfinite(a_dev).all()
+    assert worst <= 1.0, worst
 
 
 # ---------------------------------------------------------------------------------------------------------------------

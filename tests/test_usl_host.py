@@ -269,9 +269,9 @@ def test_probe_inputs_are_sized():
     reason occurs in at least 5 % of the rows of some case, at least half of all rows apply one update or more, and the
     edge rows of the single pass are at most 2 % in every case.  Observed with niter = 20 (share of stop 0 / 1 / 2, rows
     that moved, edge rows of the first pass):
-        ant256         0.052 0.414 0.534   0.278   0.0007        below-87       0.921 0.079 0.000   0.921   0
-        point64        0.278 0.099 0.623   0.429   0.0010        saturated192   0.187 0.163 0.650   0.435   0.0007
-        threshold20    0.455 0.545 0.000   0.918   0             walker128      0.056 0.483 0.462   0.284   0
+        ant256         0.052 0.415 0.533   0.278   0.0007        below-87       0.921 0.079 0.000   0.921   0
+        point64        0.278 0.099 0.623   0.429   0.0010        saturated192   0.174 0.180 0.646   0.435   0.0007
+        threshold20    0.455 0.545 0.000   0.918   0             walker128      0.055 0.482 0.463   0.284   0
         zero-gradient  0.914 0.086 0.000   0.914   0
     About 12 500 of the 21 000 rows move at least once (0.60)."""
     import test_gpu_usl as tg
@@ -293,6 +293,41 @@ def test_probe_inputs_are_sized():
         rows += len(obs)
     assert (best >= 0.05).all(), best
     assert moved_all >= 0.5 * rows, (moved_all, rows)
+
+
+def test_multi_pass_inputs_are_sized():
+    """On the rows of tests/test_gpu_usl.py's multi-pass tests (33 of each case from MULTI_ROW0[case], both gradient scales), with the
+    float64 restatement alone: some row runs all 20 passes, at least two stop reasons occur, some row moves twice or
+    more, the running sum moves such a row somewhere else than the memoryless step does (by far more than fp32
+    resolves), no row is an edge row in any pass (the GPU tests cap them at 2 % of 33 rows or fewer: none), the first row runs all
+    20 passes and a row that never moves is among the first 15."""
+    import test_gpu_usl as tg
+    for name in tg.MULTI_CASES:
+        qm, obs, act, delta = tg.probe_inputs(name)
+        n = max(tg.MULTI_ROWS)
+        r0 = tg.MULTI_ROW0[name]
+        obs, act = obs[r0:r0 + n], act[r0:r0 + n]
+        Q = usl64.QCritic(qm)
+        for gs in tg.MULTI_SCALES:
+            it = Q.iterate(obs, act, delta, tg.MULTI_PASSES, tg.ETA, gs)
+            a, acc, dacc, live, edges, gap = act.astype(np.float64), None, None, np.ones(n, bool), np.zeros(n, bool), 0.0
+            for p in range(tg.MULTI_PASSES):
+                r = Q.one_pass(obs, a, delta, tg.ETA, gs, acc=acc, dacc=dacc)
+                edges |= live & r['edge']
+                live &= r['stop'] < 0
+                if p == 1 and live.any():
+                    gap = np.abs(Q.one_pass(obs, a, delta, tg.ETA, gs)['a_next'] - r['a_next'])[live].max()
+                a, acc, dacc = r['a_next'], r['acc'], r['dacc']
+            np.testing.assert_array_equal(a, it['a_safe'])
+            print(f"usl multi-pass sizing {name} gs={gs:g}: iters {np.bincount(it['iters'], minlength=21).tolist()}  "
+                  f"stop {np.bincount(it['stop'], minlength=3).tolist()}  edge rows {int(edges.sum())}  "
+                  f"second step: running sum against memoryless {gap:.2e}")
+            assert it['iters'].max() == tg.MULTI_PASSES and len(set(it['stop'].tolist())) >= 2
+            assert (it['iters'] >= 2).any() and gap > 1e-5
+            assert not edges.any()
+            # the first row runs every pass, so the tests on 1, 15, 16 and 17 rows carry a running sum as well, and a row
+            # that never moves sits among the first 15
+            assert it['iters'][0] == tg.MULTI_PASSES and (it['iters'][:min(tg.MULTI_ROWS[1:])] == 0).any()
 
 
 @pytest.mark.parametrize("case", [0, 1, 2])

@@ -4,6 +4,13 @@ a correct fp32 evaluation in the kernel's operation order (include/guardx_usl.h)
 the numpy float32 transcription of the update step.  The weights are read from the torch module, never from a packed
 vector.
 
+The rule (usl_core.py:180-194).  safety_correction never clears act.grad: c_net.zero_grad() (182) zeroes the network's
+gradients only and act is one leaf tensor across the passes, so every pred.mean().backward() (184) ADDS to act.grad, in
+fp32.  The update of pass p (190-194) therefore uses the running sum of the passes' scaled gradients,
+    acc_p = acc_{p-1} + s_p  (acc_1 = s_1),      a = a - eta acc_p / (max_k |acc_p[k]| + 1e-8),
+not s_p alone.  one_pass and iterate carry acc; update32 takes it.  (Rows that have stopped keep accumulating in the
+reference and never move again: their sum is never read.)
+
 Bounds.  ESTIMATED like oracle/policy64.py's, from its constants (U, chain, MARGIN, SIGMAS, TANH_ABS, EXP_REL) and the
 statewise path's Softplus bound (tests/test_gpu_statewise.py:softplus_bound); exact fp32 inputs (obs, a) carry no error.
   forward   policy64.mlp's recurrence, kept per layer: pre-activation 4 sqrt(K + 1) u sum |w x| plus the inputs' error
@@ -18,8 +25,9 @@ statewise path's Softplus bound (tests/test_gpu_statewise.py:softplus_bound); ex
   sp = e / (e + 1)   sigma' = sp (1 - sp): sp (1 - sp) (dz3 + EXP_REL) + 2 u sp; + 2.1e-9 for the switch to 1 at z3 > 20,
             + 1e-37 for exp's flush to zero below -87
   c = grad_scale sp, s = c g~      one rounding each
-  Z = max |s|     dZ = max ds;  den = Z + 1e-8: dZ + u den
-  r = s / den     (ds + |r| dden) / (den - dden) + u |r|, never more than 2 (|r| <= 1 on both sides)
+  acc = acc + s   every add contributes ds plus one rounding, u |acc|, to dacc (none in a row's first pass, acc = s)
+  Z = max |acc|   dZ = max dacc;  den = Z + 1e-8: dZ + u den
+  r = acc / den   (dacc + |r| dden) / (den - dden) + u |r|, never more than 2 (|r| <= 1 on both sides)
   a' = a - eta r  eta dr + u |eta r| + u |a'|
 A row is an EDGE row when |q - delta| < dq or |max a - 1| < da at the pass: there a correct fp32 evaluation may stop where
 float64 goes on, or the reverse: such rows may differ in `stop` (and what follows from it) only, and their share is capped.
@@ -117,17 +125,23 @@ class QCritic:
         r.update(gt=gt, dgt=dgt, sp=sp, s=s, ds=ds)
         return r
 
-    def one_pass(self, obs, a, delta=0.0, eta=0.05, grad_scale=1.0, da=None):
-        """one pass of the iteration on exact fp32 rows (da: the error the actions already carry, for the edge test):
-        forward / grad's dict plus stop (-1: the row moved, 1, 2), edge, a_next and its bound da_next"""
+    def one_pass(self, obs, a, delta=0.0, eta=0.05, grad_scale=1.0, da=None, acc=None, dacc=None):
+        """one pass of the iteration on exact fp32 rows (da: the error the actions already carry, for the edge test;
+        acc, dacc: the running sum of the earlier passes' s and its bound, None in the first pass): forward / grad's
+        dict plus stop (-1: the row moved, 1, 2), edge, a_next and its bound da_next, and acc / dacc after this pass"""
         a = np.asarray(a, np.float64)
         r = self.grad(obs, a, grad_scale)
+        if acc is None:
+            acc, dacc = r['s'], r['ds']
+        else:
+            acc = np.asarray(acc, np.float64) + r['s']
+            dacc = (0.0 if dacc is None else dacc) + r['ds'] + U * np.abs(acc)
         da = np.zeros(a.shape[:-1]) if da is None else da
         mx = a.max(-1)
         stop = np.where(mx > 1.0, 1, np.where(r['q'] <= float(F(delta)), 2, -1))
         edge = (np.abs(mx - 1.0) < da) | ((mx <= 1.0) & (np.abs(r['q'] - float(F(delta))) < r['dq']))
         e32, tiny = float(F(eta)), float(F(1e-8))
-        s, ds = r['s'], r['ds']
+        s, ds = acc, dacc
         Z, dZ = np.abs(s).max(-1), ds.max(-1)
         den = Z + tiny
         dden = dZ + U * den
@@ -138,7 +152,7 @@ class QCritic:
         a_next = a - e32 * q
         da_next = MARGIN * (e32 * dq + U * np.abs(e32 * q) + U * np.abs(a_next))
         moved = stop < 0
-        r.update(stop=stop, edge=edge, a_next=np.where(moved[..., None], a_next, a),
+        r.update(acc=acc, dacc=dacc, stop=stop, edge=edge, a_next=np.where(moved[..., None], a_next, a),
                  da_next=np.where(moved[..., None], da_next, 0.0))
         return r
 
@@ -146,12 +160,13 @@ class QCritic:
         """the whole iteration in float64 (no bounds): a_safe, iters, stop (0 niter exhausted, 1, 2), q0"""
         a = np.array(a, np.float64)
         n = a.shape[0]
-        stop, iters, q0 = np.full(n, -1), np.zeros(n, np.int64), None
+        stop, iters, q0, acc = np.full(n, -1), np.zeros(n, np.int64), None, None
         for p in range(niter):
             live = stop < 0
             if not live.any():
                 break
-            r = self.one_pass(obs, a, delta, eta, grad_scale)
+            r = self.one_pass(obs, a, delta, eta, grad_scale, acc=acc)
+            acc = r['acc']
             if p == 0:
                 q0 = r['q']
             st = np.where(live, r['stop'], stop)
@@ -165,7 +180,8 @@ class QCritic:
 
 
 def update32(a, s, eta):
-    """the update of include/guardx_usl.h in numpy float32, one IEEE operation per operator: Z = |s[0]|, then
+    """the update of include/guardx_usl.h in numpy float32 from the ACCUMULATED s (the fp32 running sum of the passes'
+    scaled gradients; the first pass's s itself), one IEEE operation per operator: Z = |s[0]|, then
     Z = |s[i]| > Z ? |s[i]| : Z for i ascending; den = Z + 1e-8f; a[i] - eta * (s[i] / den)"""
     a, s = np.asarray(a, F), np.asarray(s, F)
     ab = np.abs(s)

@@ -71,8 +71,10 @@ def main():
 
             def safety_correction(o, act):
                 # usl_core.py:165-196 restated: frozen rows are kept as an index set, every pass is a forward and an
-                # autograd backward of pred.mean() through c_net, the update is normalised by the row's largest |grad|
+                # autograd backward of pred.mean() through c_net into act.grad, which the reference never clears
+                # (usl_core.py:180-194): the update uses the running sum, normalised by the row's largest |sum|
                 act = act.clone()
+                acc = None
                 rows = torch.arange(N, device='cuda')
                 frozen = torch.zeros(N, dtype=torch.bool, device='cuda')
                 with torch.no_grad():
@@ -84,6 +86,7 @@ def main():
                     act.requires_grad_()
                     pred = c_n(torch.cat((o, act), 1)).squeeze(-1)
                     grad, = torch.autograd.grad(pred.mean(), act)
+                    grad = acc = grad if acc is None else acc + grad
                     frozen |= pred.detach() <= delta
                     if bool(frozen.all()):
                         break
