@@ -5,5 +5,7 @@ from .env_config import configuration, create_env  # noqa: F401
 from .epstats import combine_episode_stats, constraint_value, episode_stats  # noqa: F401
 from . import fisher  # noqa: F401
 from .fisher import FisherOperator  # noqa: F401
+from . import linesearch  # noqa: F401
+from .linesearch import LineSearch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
-"""Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, in that order)
-for gfx950 in-tree with hipcc.
+"""Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, then of
+UPDATE_LIBRARIES, in that order) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -219,8 +219,15 @@ LIBRARIES = {lib.key: lib for lib in (
 # guardx_amd/fisher.py).  The same Library class, built after LIBRARIES and looked up beside it
 # (guardx_amd/_sidelib.py).  A mapping of its own only because tests/test_build_identity.py pins list(LIBRARIES) to the
 # nine libraries it records: folding the two mappings together waits for a pull request that may touch that test.
+# The same holds one step on: tests/test_fisher_host.py pins list(LEARNER_LIBRARIES) to fisher and every_library() to
+# MAIN and these two mappings, so what came after it -- linesearch (the TRPO family's backtracking line search,
+# guardx_amd/linesearch.py) -- is a third mapping, UPDATE_LIBRARIES, built last and reached through all_libraries().
 LEARNER_LIBRARIES = {lib.key: lib for lib in (
     _side("fisher", "GXF_BUILD_ID", _SIDE_HEADERS),
+)}
+
+UPDATE_LIBRARIES = {lib.key: lib for lib in (
+    _side("linesearch", "GXB_BUILD_ID", _SIDE_HEADERS),
 )}
 
 
@@ -229,15 +236,20 @@ def every_library():
     return [MAIN] + list(LIBRARIES.values()) + list(LEARNER_LIBRARIES.values())
 
 
+def all_libraries():
+    """every_library() and UPDATE_LIBRARIES, in build order: what build() builds and the bindings look up"""
+    return every_library() + list(UPDATE_LIBRARIES.values())
+
+
 def build(force=False, verbose=False, jobs=None):
     """Build what needs building under an inter-process lock (several ranks importing at once build once).  Every
-    library of every_library(); returns the path of libguardx_hip.so."""
+    library of all_libraries(); returns the path of libguardx_hip.so."""
     import fcntl
     os.makedirs(LIB_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for lib in every_library():
+            for lib in all_libraries():
                 if force or lib.needs_build():
                     lib.build(verbose, jobs, force)
             return LIB
@@ -248,5 +260,5 @@ def build(force=False, verbose=False, jobs=None):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in every_library()[1:]:
+    for side in all_libraries()[1:]:
         print(side.key, "build id", side.built_id())
