@@ -7,5 +7,7 @@ from . import fisher  # noqa: F401
 from .fisher import FisherOperator  # noqa: F401
 from . import linesearch  # noqa: F401
 from .linesearch import LineSearch  # noqa: F401
+from . import vfit  # noqa: F401
+from .vfit import ValueFit  # noqa: F401
 
 __version__ = "0.1.0"

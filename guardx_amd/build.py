@@ -1,5 +1,5 @@
 """Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, then of
-UPDATE_LIBRARIES, in that order) for gfx950 in-tree with hipcc.
+UPDATE_LIBRARIES, then of FIT_LIBRARIES, in that order) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -221,13 +221,20 @@ LIBRARIES = {lib.key: lib for lib in (
 # nine libraries it records: folding the two mappings together waits for a pull request that may touch that test.
 # The same holds one step on: tests/test_fisher_host.py pins list(LEARNER_LIBRARIES) to fisher and every_library() to
 # MAIN and these two mappings, so what came after it -- linesearch (the TRPO family's backtracking line search,
-# guardx_amd/linesearch.py) -- is a third mapping, UPDATE_LIBRARIES, built last and reached through all_libraries().
+# guardx_amd/linesearch.py) -- is a third mapping, UPDATE_LIBRARIES, reached through all_libraries().
+# And once more: tests/test_linesearch_host.py pins list(UPDATE_LIBRARIES) to linesearch and all_libraries() to the eleven
+# libraries up to it, so vfit (the critics' Adam fit, guardx_amd/vfit.py) is a fourth mapping, FIT_LIBRARIES, built last and
+# reached through fit_libraries(): that is the list build() builds and the bindings look up.
 LEARNER_LIBRARIES = {lib.key: lib for lib in (
     _side("fisher", "GXF_BUILD_ID", _SIDE_HEADERS),
 )}
 
 UPDATE_LIBRARIES = {lib.key: lib for lib in (
     _side("linesearch", "GXB_BUILD_ID", _SIDE_HEADERS),
+)}
+
+FIT_LIBRARIES = {lib.key: lib for lib in (
+    _side("vfit", "GXV_BUILD_ID", _SIDE_HEADERS),
 )}
 
 
@@ -237,19 +244,25 @@ def every_library():
 
 
 def all_libraries():
-    """every_library() and UPDATE_LIBRARIES, in build order: what build() builds and the bindings look up"""
+    """every_library() and UPDATE_LIBRARIES, in build order"""
     return every_library() + list(UPDATE_LIBRARIES.values())
+
+
+def fit_libraries():
+    """all_libraries() and FIT_LIBRARIES, in build order: every library there is; what build() builds and the bindings
+    look up"""
+    return all_libraries() + list(FIT_LIBRARIES.values())
 
 
 def build(force=False, verbose=False, jobs=None):
     """Build what needs building under an inter-process lock (several ranks importing at once build once).  Every
-    library of all_libraries(); returns the path of libguardx_hip.so."""
+    library of fit_libraries(); returns the path of libguardx_hip.so."""
     import fcntl
     os.makedirs(LIB_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for lib in all_libraries():
+            for lib in fit_libraries():
                 if force or lib.needs_build():
                     lib.build(verbose, jobs, force)
             return LIB
@@ -260,5 +273,5 @@ def build(force=False, verbose=False, jobs=None):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in all_libraries()[1:]:
+    for side in fit_libraries()[1:]:
         print(side.key, "build id", side.built_id())
