@@ -1,5 +1,5 @@
 """Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, then of
-UPDATE_LIBRARIES, then of FIT_LIBRARIES, in that order) for gfx950 in-tree with hipcc.
+UPDATE_LIBRARIES, then of FIT_LIBRARIES, then of GRAD_LIBRARIES, in that order) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -224,7 +224,10 @@ LIBRARIES = {lib.key: lib for lib in (
 # guardx_amd/linesearch.py) -- is a third mapping, UPDATE_LIBRARIES, reached through all_libraries().
 # And once more: tests/test_linesearch_host.py pins list(UPDATE_LIBRARIES) to linesearch and all_libraries() to the eleven
 # libraries up to it, so vfit (the critics' Adam fit, guardx_amd/vfit.py) is a fourth mapping, FIT_LIBRARIES, built last and
-# reached through fit_libraries(): that is the list build() builds and the bindings look up.
+# reached through fit_libraries().
+# And a fourth time: tests/test_vfit_host.py pins list(FIT_LIBRARIES) to vfit and fit_libraries() to the twelve libraries up
+# to it, so pgrad (the surrogate gradients g and b and CPO's step direction, guardx_amd/pgrad.py) is a fifth mapping,
+# GRAD_LIBRARIES, built last and reached through grad_libraries(): that is the list build() builds and the bindings look up.
 LEARNER_LIBRARIES = {lib.key: lib for lib in (
     _side("fisher", "GXF_BUILD_ID", _SIDE_HEADERS),
 )}
@@ -235,6 +238,11 @@ UPDATE_LIBRARIES = {lib.key: lib for lib in (
 
 FIT_LIBRARIES = {lib.key: lib for lib in (
     _side("vfit", "GXV_BUILD_ID", _SIDE_HEADERS),
+)}
+
+
+GRAD_LIBRARIES = {lib.key: lib for lib in (
+    _side("pgrad", "GXG_BUILD_ID", _SIDE_HEADERS),
 )}
 
 
@@ -249,20 +257,25 @@ def all_libraries():
 
 
 def fit_libraries():
-    """all_libraries() and FIT_LIBRARIES, in build order: every library there is; what build() builds and the bindings
-    look up"""
+    """all_libraries() and FIT_LIBRARIES, in build order"""
     return all_libraries() + list(FIT_LIBRARIES.values())
+
+
+def grad_libraries():
+    """fit_libraries() and GRAD_LIBRARIES, in build order: every library there is; what build() builds and the bindings
+    look up"""
+    return fit_libraries() + list(GRAD_LIBRARIES.values())
 
 
 def build(force=False, verbose=False, jobs=None):
     """Build what needs building under an inter-process lock (several ranks importing at once build once).  Every
-    library of fit_libraries(); returns the path of libguardx_hip.so."""
+    library of grad_libraries(); returns the path of libguardx_hip.so."""
     import fcntl
     os.makedirs(LIB_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for lib in fit_libraries():
+            for lib in grad_libraries():
                 if force or lib.needs_build():
                     lib.build(verbose, jobs, force)
             return LIB
@@ -273,5 +286,5 @@ def build(force=False, verbose=False, jobs=None):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in fit_libraries()[1:]:
+    for side in grad_libraries()[1:]:
         print(side.key, "build id", side.built_id())
