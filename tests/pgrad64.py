@@ -94,20 +94,23 @@ def pool(errs):
 # ---------------------------------------------------------------------------------------------------------------------
 # CPO's direction
 # ---------------------------------------------------------------------------------------------------------------------
-def cpo_direction64(b, Hinv_g, Hinv_b, approx_g, s, c, target_kl):
-    """The header's ladder on numpy float64: -> dict(optim_case, lam, nu, q, r, s, A, B, x, f_a_wins, la_first).  f_a_wins
-    and la_first (cases 1 and 2 only, else None) say which of f_a >= f_b and c < 0 (LA before LB) held."""
+def cpo_direction64(b, Hinv_g, Hinv_b, approx_g, s, c, target_kl, dots=None):
+    """The header's ladder on numpy float64: -> dict(optim_case, lam, nu, q, r, s, A, B, x, f_a_wins, la_first, bb, f_a, f_b).
+    f_a_wins and la_first (cases 1 and 2 only, else None) say which of f_a >= f_b and c < 0 (LA before LB) held; f_a and f_b are
+    the two values compared there.  `dots`: dict(q, r, bb), the three dots as a caller took them (the learners take theirs
+    in float32: tests/update64.py), in place of the float64 ones of the vectors."""
     b, Hinv_g, Hinv_b, approx_g = (np.asarray(v, dtype=np.float64) for v in (b, Hinv_g, Hinv_b, approx_g))
     s, c, tkl = float(s), float(c), float(target_kl)
-    q = float(Hinv_g @ approx_g)
-    f_a_wins = la_first = None
+    q = float(Hinv_g @ approx_g) if dots is None else float(dots["q"])
+    bb = float(b @ b) if dots is None else float(dots["bb"])
+    f_a_wins = la_first = f_a = f_b = None
     with np.errstate(all="ignore"):
-        if float(b @ b) <= 1e-8 and c < 0:
+        if bb <= 1e-8 and c < 0:
             Hinv_b = np.zeros_like(Hinv_g)
             r = s = A = B = 0.0
             case = 4
         else:
-            r = float(Hinv_b @ approx_g)
+            r = float(Hinv_b @ approx_g) if dots is None else float(dots["r"])
             A = q - r * r / s
             B = 2.0 * tkl - c * c / s
             case = 3 if (c < 0 and B < 0) else 2 if (c < 0 and B >= 0) else 1 if (c >= 0 and B >= 0) else 0
@@ -128,7 +131,8 @@ def cpo_direction64(b, Hinv_g, Hinv_b, approx_g, s, c, target_kl):
         else:
             lam, nu = 0.0, math.sqrt(2.0 * tkl / (s + EPS))
         x = (1.0 / (lam + EPS)) * (Hinv_g + nu * Hinv_b) if case > 0 else nu * Hinv_b
-    return dict(optim_case=case, lam=lam, nu=nu, q=q, r=r, s=s, A=A, B=B, x=x, f_a_wins=f_a_wins, la_first=la_first)
+    return dict(optim_case=case, lam=lam, nu=nu, q=q, r=r, s=s, A=A, B=B, x=x, f_a_wins=f_a_wins, la_first=la_first, bb=bb,
+                f_a=f_a, f_b=f_b)
 
 
 SITUATIONS = ("case0", "case1_fa", "case1_fb", "case2_fa", "case2_fb", "case3", "case4")
