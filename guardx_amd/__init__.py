@@ -11,5 +11,7 @@ from . import vfit  # noqa: F401
 from .vfit import ValueFit  # noqa: F401
 from . import pgrad  # noqa: F401
 from .pgrad import SurrogateGradient, cpo_direction, trpo_direction  # noqa: F401
+from . import pifit  # noqa: F401
+from .pifit import PolicyFit  # noqa: F401
 
 __version__ = "0.1.0"

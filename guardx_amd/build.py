@@ -1,5 +1,6 @@
 """Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, then of
-UPDATE_LIBRARIES, then of FIT_LIBRARIES, then of GRAD_LIBRARIES, in that order) for gfx950 in-tree with hipcc.
+UPDATE_LIBRARIES, then of FIT_LIBRARIES, then of GRAD_LIBRARIES, then of ACTOR_LIBRARIES, in that order) for gfx950 in-tree
+with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -227,7 +228,10 @@ LIBRARIES = {lib.key: lib for lib in (
 # reached through fit_libraries().
 # And a fourth time: tests/test_vfit_host.py pins list(FIT_LIBRARIES) to vfit and fit_libraries() to the twelve libraries up
 # to it, so pgrad (the surrogate gradients g and b and CPO's step direction, guardx_amd/pgrad.py) is a fifth mapping,
-# GRAD_LIBRARIES, built last and reached through grad_libraries(): that is the list build() builds and the bindings look up.
+# GRAD_LIBRARIES, built last and reached through grad_libraries().
+# And a fifth time: tests/test_pgrad_host.py pins list(GRAD_LIBRARIES) to pgrad and grad_libraries() to the thirteen libraries up
+# to it, so pifit (the PPO family's Adam fit of the actor on the clipped surrogate, guardx_amd/pifit.py) is a sixth mapping,
+# ACTOR_LIBRARIES, built last and reached through actor_libraries(): that is the list build() builds and the bindings look up.
 LEARNER_LIBRARIES = {lib.key: lib for lib in (
     _side("fisher", "GXF_BUILD_ID", _SIDE_HEADERS),
 )}
@@ -243,6 +247,11 @@ FIT_LIBRARIES = {lib.key: lib for lib in (
 
 GRAD_LIBRARIES = {lib.key: lib for lib in (
     _side("pgrad", "GXG_BUILD_ID", _SIDE_HEADERS),
+)}
+
+
+ACTOR_LIBRARIES = {lib.key: lib for lib in (
+    _side("pifit", "GXA_BUILD_ID", _SIDE_HEADERS),
 )}
 
 
@@ -262,20 +271,25 @@ def fit_libraries():
 
 
 def grad_libraries():
-    """fit_libraries() and GRAD_LIBRARIES, in build order: every library there is; what build() builds and the bindings
-    look up"""
+    """fit_libraries() and GRAD_LIBRARIES, in build order"""
     return fit_libraries() + list(GRAD_LIBRARIES.values())
+
+
+def actor_libraries():
+    """grad_libraries() and ACTOR_LIBRARIES, in build order: every library there is; what build() builds and the bindings
+    look up"""
+    return grad_libraries() + list(ACTOR_LIBRARIES.values())
 
 
 def build(force=False, verbose=False, jobs=None):
     """Build what needs building under an inter-process lock (several ranks importing at once build once).  Every
-    library of grad_libraries(); returns the path of libguardx_hip.so."""
+    library of actor_libraries(); returns the path of libguardx_hip.so."""
     import fcntl
     os.makedirs(LIB_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for lib in grad_libraries():
+            for lib in actor_libraries():
                 if force or lib.needs_build():
                     lib.build(verbose, jobs, force)
             return LIB
@@ -286,5 +300,5 @@ def build(force=False, verbose=False, jobs=None):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in grad_libraries()[1:]:
+    for side in actor_libraries()[1:]:
         print(side.key, "build id", side.built_id())

@@ -13,9 +13,9 @@ get_net_param_np_vec has them (fisher.flat_params).
 A loss with a Lagrangian term, trpolag's and trpofac's loss_pi = -mean(ratio adv) + lmd mean(ratio adc), is linear in the
 row weight: pass adv - lmd adc as adv, as for the line search.
 
-Not served: mpi_avg_grads (several ranks averaging their gradients), apo's variance loss, PPO's clipped loss and its Adam
-loop on the actor (the same kernel with a clipped row weight), pcpo's direction (its ladder projects with H^-1 b onto the
-constraint instead of solving CPO's dual).
+Not served: mpi_avg_grads (several ranks averaging their gradients), apo's variance loss, pcpo's direction (its ladder
+projects with H^-1 b onto the constraint instead of solving CPO's dual).  PPO's clipped loss and its Adam loop on the actor
+are guardx_amd.pifit: the same kernel with a clipped row weight.
 """
 import torch
 
