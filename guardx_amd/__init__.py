@@ -13,5 +13,7 @@ from . import pgrad  # noqa: F401
 from .pgrad import SurrogateGradient, cpo_direction, trpo_direction  # noqa: F401
 from . import pifit  # noqa: F401
 from .pifit import PolicyFit  # noqa: F401
+from . import cfit  # noqa: F401
+from .cfit import CostCriticFit  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,4 +1,5 @@
-"""What the ctypes bindings of the libraries (guardx_amd/build.py: actor_libraries()) share: load(), check() and
+"""What the ctypes bindings of the libraries (guardx_amd/build.py: actor_libraries() and what safety_libraries() adds to
+it) share: load(), check() and
 the error class.  There is no CPU fallback: a missing library is built in place with hipcc, and a library built from
 other sources than the tree's is refused.
 """
@@ -21,7 +22,7 @@ class Binding:
     whose build id is then not checked; `loaded(lib)` runs once on the library that passed."""
 
     def __init__(self, key, prefix, symbols, ok, label, other_path=None, loaded=None):
-        self.side = {lib.key: lib for lib in _build.actor_libraries()}[key]
+        self.side = {lib.key: lib for lib in _build.safety_libraries()}[key]
         self.prefix, self.symbols, self.ok = prefix, symbols, ok
         self.path = self.side.lib
         self.other_path, self.loaded = other_path, loaded

@@ -1,6 +1,6 @@
 """Build the project's shared libraries (MAIN, then every entry of LIBRARIES, then of LEARNER_LIBRARIES, then of
-UPDATE_LIBRARIES, then of FIT_LIBRARIES, then of GRAD_LIBRARIES, then of ACTOR_LIBRARIES, in that order) for gfx950 in-tree
-with hipcc.
+UPDATE_LIBRARIES, then of FIT_LIBRARIES, then of GRAD_LIBRARIES, then of ACTOR_LIBRARIES, then of SAFETY_LIBRARIES, in that
+order) for gfx950 in-tree with hipcc.
 
     python -m guardx_amd.build [--force]
 
@@ -231,7 +231,10 @@ LIBRARIES = {lib.key: lib for lib in (
 # GRAD_LIBRARIES, built last and reached through grad_libraries().
 # And a fifth time: tests/test_pgrad_host.py pins list(GRAD_LIBRARIES) to pgrad and grad_libraries() to the thirteen libraries up
 # to it, so pifit (the PPO family's Adam fit of the actor on the clipped surrogate, guardx_amd/pifit.py) is a sixth mapping,
-# ACTOR_LIBRARIES, built last and reached through actor_libraries(): that is the list build() builds and the bindings look up.
+# ACTOR_LIBRARIES, built last and reached through actor_libraries().
+# And a sixth time: tests/test_pifit_host.py pins list(ACTOR_LIBRARIES) to pifit and actor_libraries() to the fourteen libraries
+# up to it, so cfit (the safety critics' Adam fit under row weights, guardx_amd/cfit.py) is a seventh mapping, SAFETY_LIBRARIES,
+# built last and reached through safety_libraries(): that is the list build() builds and the bindings look up.
 LEARNER_LIBRARIES = {lib.key: lib for lib in (
     _side("fisher", "GXF_BUILD_ID", _SIDE_HEADERS),
 )}
@@ -252,6 +255,11 @@ GRAD_LIBRARIES = {lib.key: lib for lib in (
 
 ACTOR_LIBRARIES = {lib.key: lib for lib in (
     _side("pifit", "GXA_BUILD_ID", _SIDE_HEADERS),
+)}
+
+
+SAFETY_LIBRARIES = {lib.key: lib for lib in (
+    _side("cfit", "GXQ_BUILD_ID", _SIDE_HEADERS),
 )}
 
 
@@ -276,20 +284,25 @@ def grad_libraries():
 
 
 def actor_libraries():
-    """grad_libraries() and ACTOR_LIBRARIES, in build order: every library there is; what build() builds and the bindings
-    look up"""
+    """grad_libraries() and ACTOR_LIBRARIES, in build order"""
     return grad_libraries() + list(ACTOR_LIBRARIES.values())
+
+
+def safety_libraries():
+    """actor_libraries() and SAFETY_LIBRARIES, in build order: every library there is; what build() builds and the bindings
+    look up"""
+    return actor_libraries() + list(SAFETY_LIBRARIES.values())
 
 
 def build(force=False, verbose=False, jobs=None):
     """Build what needs building under an inter-process lock (several ranks importing at once build once).  Every
-    library of actor_libraries(); returns the path of libguardx_hip.so."""
+    library of safety_libraries(); returns the path of libguardx_hip.so."""
     import fcntl
     os.makedirs(LIB_DIR, exist_ok=True)
     with open(LOCK_FILE, "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            for lib in actor_libraries():
+            for lib in safety_libraries():
                 if force or lib.needs_build():
                     lib.build(verbose, jobs, force)
             return LIB
@@ -300,5 +313,5 @@ def build(force=False, verbose=False, jobs=None):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("build id", built_id())
-    for side in actor_libraries()[1:]:
+    for side in safety_libraries()[1:]:
         print(side.key, "build id", side.built_id())

@@ -12,8 +12,9 @@ launches per iteration, no autograd graph, nothing synchronised (libguardx_vfit.
 The gradient of the loss is taken in closed form over the MLP critic (hidden width 64, tanh, one linear output) and Adam is
 torch's single-tensor form.  Vectors are in the order of critic.parameters(): W1 b1 W2 b2 W3 b3.
 
-Not served: mpi_avg_grads (several ranks averaging their gradients), SCPO's down-sampled vc loss with its softplus head,
-mini-batches (the reference has none), weight decay and amsgrad.
+Not served: mpi_avg_grads (several ranks averaging their gradients), mini-batches (the reference has none), weight decay and
+amsgrad.  SCPO's down-sampled vc loss with its softplus head, and the cost critics of usl, lpg and safelayer, are
+guardx_amd.cfit's (CostCriticFit).
 """
 import ctypes as C
 
